@@ -1,6 +1,8 @@
 """Benchmark: scored (user, candidate) pairs/s of the MINER scoring path on MI355X.
 
     python bench.py [--gpus N --steps K --warmup W]          # N=1 default; N>1 spawns N ranks itself
+    python bench.py --full                                   # + every sub-line, baseline and check
+    python bench.py --dump-outputs DIR                       # + the last timed step's scores as .npy
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -16,14 +18,22 @@ GPU (default 3,000,000 = the whole MIND-large-shaped eval set per GPU); impressi
 across ranks with no collective on the data path (weak scaling); ``value`` = pairs scored by all
 ranks / max-over-ranks time.
 
-Also on the line: ``roofline`` of the scoring kernel on SURVEY §8(d)'s algorithmic bytes
-((L+C)·d·4 + L + 4C per impression) over its HIP-event launch time, with the MFMA fraction of its
-contraction FLOPs beside it and the bytes it really gathers (``gathered_bytes``); the bf16
-throughput mode of the same path (``bf16_mode``, with its AUC delta); config 2 (d=256, 50k
-impressions); the metric step (per-impression metrics + exact global AUC on the device); the fused
-dense-row kernel; the AUC parity of the GPU path against the reference CPU path on a sample; and
-the CPU baseline (the oracle — the reference's torch CPU path restated — on this host's cores) at
-N=1.
+A plain run sets up, warms up, times the K steps and prints the line: the headline, the ``roofline``
+of the scoring kernel on SURVEY §8(d)'s algorithmic bytes ((L+C)·d·4 + L + 4C per impression) over
+its HIP-event launch time in those same steps, with the MFMA fraction of its contraction FLOPs
+beside it and the bytes it really gathers (``gathered_bytes``), and the precompute's share. Every
+other field of the line is null. ``--dump-outputs DIR`` writes the scores of the last timed step
+to DIR/scores.npy (float32; a fixed seeded sample of the rows, in row order, when the array is
+past the 64 MB cap); the inputs are seeded, so two builds run with the same arguments can be
+compared output for output.
+
+``--full`` adds everything that takes runs of its own: the bf16 throughput mode of the same path
+(``bf16_mode``, with its AUC delta); config 2 (d=256, 50k impressions), configs 4 and 5 and the
+wide news line; the exact fp32-MFMA kernel, the eval-with-loss and full-history launches; the metric
+step (per-impression metrics + exact global AUC on the device); the fused dense-row kernel; the AUC
+parity of the GPU path against the reference CPU path on a sample; and the CPU baseline (the
+oracle — the reference's torch CPU path restated — on this host's cores) at N=1. The other
+workloads keep their fp32 parity launches and CPU baselines behind it too.
 
 ``--workload fastformer`` measures BASELINE config 4 (FastFormer user encoder), ``--workload corpus``
 config 5 (full-corpus ranking), ``--workload config3-dense`` the fused kernel on [B, L, d] rows.
@@ -112,6 +122,32 @@ def timed_steps(step, steps, warmup, world, dev):
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
     return elapsed
+
+
+DUMP_BYTES = 60_000_000     # --dump-outputs: all arrays together stay under 64 MB on disk
+DUMP_SEED = 20
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs DIR: what the last timed step returned, as DIR/<name>.npy. Floating-point
+    arrays are written as float32 (float64 stays float64), integer arrays (top-k indices) as float64.
+    An array past its share of DUMP_BYTES is written as a sample of its rows: the same seeded row
+    set on every run, in ascending row order, so two builds can be compared output for output."""
+    if not path:
+        return
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    share = DUMP_BYTES // max(len(arrays), 1)
+    for name, t in arrays.items():
+        t = t.detach()
+        dt = torch.float64 if (t.dtype == torch.float64 or not t.dtype.is_floating_point) else torch.float32
+        row_bytes = max(t.numel() // max(t.shape[0], 1), 1) * (8 if dt == torch.float64 else 4)
+        keep = max(1, share // row_bytes)
+        if t.shape[0] > keep:
+            g = torch.Generator().manual_seed(DUMP_SEED)
+            rows = torch.randperm(t.shape[0], generator=g)[:keep].sort().values
+            t = t[rows.to(t.device)]
+        np.save(os.path.join(path, name + ".npy"), t.to("cpu", dt).numpy())
 
 
 class EventTimer:
@@ -546,17 +582,20 @@ def run_news(args, rank, world, dev):
     # the dense-row comparison line first: measured after the minute of fp32 / bf16 news launches
     # below it read 3.53-3.59 ms, in isolation every version of the kernel since round-1 v8 reads
     # 3.26-3.37 ms (tools/bisect_dense.py, profiles/r02_dense_bisect.txt)
+    full = args.full      # everything but the headline's own timed steps is measured under --full only
     dense = dense_kernel_line(dev, pmc_paths={"bf16": args.traffic, "fp32": args.traffic_dense32}) \
-        if (world == 1 and not args.no_dense) else None
+        if (full and world == 1 and not args.no_dense) else None
 
     # headline: fp32 (the reference's precision) on the fp16 matrix cores (exact-sum fp16 pairs)
     el32, pre32, kern32, o32, nt32 = measure_news(table32, W1, Q, W2, pool, args.steps, args.warmup, world, dev,
                                                   x2=True)
     s32 = o32[0]
     assert torch.isfinite(s32).all()
+    if rank == 0:
+        dump_outputs(args.dump_outputs, {"scores": o32[(args.steps - 1) % len(pool)]})
     # the exact fp32-MFMA kernel (news_score32) on the same batch: the fp32-fma-chain reference form
     exact = None
-    if world == 1 and not args.no_exact:
+    if full and world == 1 and not args.no_exact:
         n_ex = min(args.steps, 5)
         elx, prex, kernx, ox, _ = measure_news(table32, W1, Q, W2, pool, n_ex, 1, world, dev, x2=False)
         d_ex = (ox[0].double() - s32.double()).abs().max() / s32.double().pow(2).mean().sqrt()
@@ -570,7 +609,7 @@ def run_news(args, rank, world, dev):
     # the reference's default eval (config/eval_miner.txt: --evaluation_info metrics loss): the same
     # kernel with the eval loss's disagreement formed in its epilogue (no mui written)
     loss_line = None
-    if world == 1 and not args.no_exact:
+    if full and world == 1 and not args.no_exact:
         from miner_amd import news as _news
         hid0, mask0, cid0 = pool[0]
         res = [None]
@@ -591,7 +630,7 @@ def run_news(args, rank, world, dev):
         del res
     # every history full (hist_len = L, no left padding): the masked-slot grouping saves nothing here
     full_hist = None
-    if world == 1 and not args.no_exact:
+    if full and world == 1 and not args.no_exact:
         pool_f = [news_batch(4000, B, N_NEWS, dev, full=True)]
         n_f = min(args.steps, 5)
         elf, _, kernf, _, _ = measure_news(table32, W1, Q, W2, pool_f, n_f, 1, world, dev, x2=True)
@@ -607,13 +646,15 @@ def run_news(args, rank, world, dev):
                      "vs_headline_kernel_ms": round(kernf / kern32, 4)}
         del pool_f
     # bf16 throughput mode, same batch and protocol
-    table16 = table32.to(torch.bfloat16)
-    el16, pre16, kern16, o16, nt16 = measure_news(table16, W1, Q, W2, pool, args.steps, args.warmup, world, dev)
-    s16 = o16[0]
-    assert torch.isfinite(s16).all()
+    el16 = s16 = None
+    if full:
+        table16 = table32.to(torch.bfloat16)
+        el16, pre16, kern16, o16, nt16 = measure_news(table16, W1, Q, W2, pool, args.steps, args.warmup, world, dev)
+        s16 = o16[0]
+        assert torch.isfinite(s16).all()
     # N > 1: the per-GPU weak-scaling figure (NEWS_B impressions on every rank)
     weak = None
-    if world > 1 and not args.no_weak:
+    if full and world > 1 and not args.no_weak:
         del o16
         pw_ = [news_batch(5000 + rank, NEWS_B, N_NEWS, dev)]
         n_w = min(args.steps, 5)
@@ -622,22 +663,23 @@ def run_news(args, rank, world, dev):
                 "steps": n_w, "value": round(NEWS_B * C * n_w * world / elw, 1), "unit": "pairs/s",
                 "ms_per_step": round(elw / n_w * 1e3, 4), "kernel_ms_rank0": round(kernw, 4)}
         del pw_
-    c2 = config2_line(args, rank, world, dev) if not args.no_config2 else None
-    c4 = config4_subline(dev, pmc_path=args.traffic_ff) if (world == 1 and not args.no_config2) else None
-    c5 = config5_subline(dev, pmc_path=args.traffic_rk) if (world == 1 and not args.no_config2) else None
-    wide = wide_news_subline(dev) if (world == 1 and not args.no_config2) else None
+    subs = full and not args.no_config2
+    c2 = config2_line(args, rank, world, dev) if subs else None
+    c4 = config4_subline(dev, pmc_path=args.traffic_ff) if (subs and world == 1) else None
+    c5 = config5_subline(dev, pmc_path=args.traffic_rk) if (subs and world == 1) else None
+    wide = wide_news_subline(dev) if (subs and world == 1) else None
 
     if rank != 0:
         return
     value = total * C * args.steps / el32
     pmc32 = load_pmc(args.news_traffic32, f"news_L{L}_K{K}_d{D}_C{C}_N{N_NEWS}_fp32", B, "news_x2")
-    pmc16 = load_pmc(args.news_traffic, f"news_L{L}_K{K}_d{D}_C{C}_N{N_NEWS}_bf16", B, "news")
+    pmc16 = load_pmc(args.news_traffic, f"news_L{L}_K{K}_d{D}_C{C}_N{N_NEWS}_bf16", B, "news") if full else None
     roof = roofline_news(B, kern32, 4, pmc=pmc32, mode="x2",
                          kernel="news_score_x2<weighted, dense, fp16-pair operands, 12 chunks, MIND shape>")
     pre_fl = news_precompute_flops(N_NEWS, D, DC, K)
     # metric step on the device over the whole fp32 batch, and the bf16 AUC delta at full size
     metric_step = None
-    if not args.no_metrics:
+    if full and not args.no_metrics:
         lab, offs, m32, (ms, ms_first) = device_metrics(s32, dev)
         from miner_amd import metrics
         m16 = metrics.compute_metrics(torch.sigmoid(s16.float()).reshape(-1), lab.reshape(-1), offs, list(m32))
@@ -647,16 +689,18 @@ def run_news(args, rank, world, dev):
                        "fp32": {k: round(float(v), 6) for k, v in m32.items()},
                        "bf16_delta": {k: float(m16[k] - m32[k]) for k in m32},
                        "cpu_reference": metric_step_cpu_baseline() if (world == 1 and not args.no_cpu) else None}
-    bf16_mode = {"value": round(total * C * args.steps / el16, 1), "unit": "pairs/s",
+    bf16_mode = None if not full else {
+                 "value": round(total * C * args.steps / el16, 1), "unit": "pairs/s",
                  "ms_per_step": round(el16 / args.steps * 1e3, 4), "precompute_ms": round(pre16, 4),
                  "roofline": roofline_news(B, kern16, 2, pmc=pmc16, kernel="news_score<bf16,weighted,6 chunks>",
                                            mode="bf16"),
                  "auc_delta_vs_fp32": metric_step["bf16_delta"]["auc"] if metric_step else None,
                  "note": "bf16 operands, fp32 accumulation: no reference counterpart (the reference evaluates "
                          "in fp32); its metric deltas vs the fp32 headline are in metric_step.bf16_delta"}
-    with_host = host_tolist_line(s32, el32 / args.steps * 1e3) if world == 1 else None
-    cpu = cpu_baseline(args.cpu_seconds) if (world == 1 and not args.no_cpu) else None
-    auc = auc_parity(s32, s16, pool[0], table32, W1, Q, W2, dev) if (world == 1 and not args.no_cpu) else None
+    with_host = host_tolist_line(s32, el32 / args.steps * 1e3) if (full and world == 1) else None
+    cpu = cpu_baseline(args.cpu_seconds) if (full and world == 1 and not args.no_cpu) else None
+    auc = auc_parity(s32, s16, pool[0], table32, W1, Q, W2, dev) \
+        if (full and world == 1 and not args.no_cpu) else None
     line = {
         "metric": METRIC,
         "value": round(value, 1), "unit": "pairs/s", "n_gpus": world, "steps": args.steps,
@@ -848,8 +892,10 @@ def run_fastformer(args, rank, world, dev):
     elapsed = timed_steps(step, args.steps, args.warmup, world, dev)
     kern_ms = tm.mean_ms(0)
     assert torch.isfinite(out[0]).all()
+    if rank == 0:
+        dump_outputs(args.dump_outputs, {"scores": out[0]})
     f32 = None
-    if args.fp32_steps > 0:
+    if args.full and args.fp32_steps > 0:
         hist, mask, cand = pool[0]
         n32 = min(B, 5000)
         h32, c32, m32 = hist[:n32].float(), cand[:n32].float(), mask[:n32]
@@ -877,7 +923,7 @@ def run_fastformer(args, rank, world, dev):
             "flops_per_launch": fl, "kernel_ms": round(kern_ms, 4)}
     roof_hbm = {"bound": "hbm", "achieved": round(gbs, 1), "peak": PEAK_HBM_GBS, "unit": "GB/s",
                 "frac": round(gbs / PEAK_HBM_GBS, 4), "algorithmic_bytes_per_launch": by}
-    cpu = ff_cpu_baseline(args.cpu_seconds) if (world == 1 and not args.no_cpu) else None
+    cpu = ff_cpu_baseline(args.cpu_seconds) if (args.full and world == 1 and not args.no_cpu) else None
     line = {
         "metric": "(user,candidate) scores/sec, FastFormer user encoder (config 4)",
         "value": round(value, 1), "unit": "pairs/s", "n_gpus": world, "steps": args.steps,
@@ -1127,13 +1173,13 @@ def run_corpus(args, rank, world, dev):
         if e:
             e[2].record(tm.stream)
 
-    steps = args.steps if args.steps_set else 5
-    warm = args.warmup if args.warmup_set else 1
+    steps, warm = args.steps, args.warmup
     elapsed = timed_steps(step, steps, warm, world, dev)
     enc_ms, rank_ms = tm.mean_ms(0), tm.mean_ms(1)
     assert torch.isfinite(out[0][0]).all()
     if rank != 0:
         return
+    dump_outputs(args.dump_outputs, {"topk_scores": out[0][0], "topk_index": out[0][1]})
     pairs = U * C5_N
     fl = pairs * 4 * C5_K * D            # M = mui·e and Lg = proj·e per (user, news) pair (model.py:127, :213)
     tflops = fl / (rank_ms / 1e3) / 1e12
@@ -1152,7 +1198,8 @@ def run_corpus(args, rank, world, dev):
                      "flops_per_launch": fl, "kernel_ms": round(rank_ms, 3)},
         "encoder": {"kernel": "ue_fused<fp16>", "ms": round(enc_ms, 3),
                     "tflops": round(enc_fl / (enc_ms / 1e3) / 1e12, 2)},
-        "cpu_baseline": corpus_cpu_baseline(min(args.cpu_seconds, 10.0)) if (world == 1 and not args.no_cpu) else None,
+        "cpu_baseline": corpus_cpu_baseline(min(args.cpu_seconds, 10.0))
+        if (args.full and world == 1 and not args.no_cpu) else None,
     }
     print(json.dumps(line), flush=True)
 
@@ -1187,6 +1234,7 @@ def run_dense(args, rank, world, dev):
     assert torch.isfinite(out[0]).all()
     if rank != 0:
         return
+    dump_outputs(args.dump_outputs, {"scores": out[0]})
     fl = flops_per_impression(L, K, D, DC, C) * B
     by = bytes_per_impression(L, D, C, 2) * B
     tflops = fl / (kern_ms / 1e3) / 1e12
@@ -1208,7 +1256,7 @@ def run_dense(args, rank, world, dev):
                      "mfma_busy_pmc": pmc.get("mfma_busy_frac") if pmc else None},
         "roofline_hbm": {"bound": "hbm", "achieved": round(gbs, 1), "peak": PEAK_HBM_GBS, "unit": "GB/s",
                          "frac": round(gbs / PEAK_HBM_GBS, 4), "algorithmic_bytes_per_launch": by},
-        "cpu_baseline": cpu_baseline(args.cpu_seconds) if (world == 1 and not args.no_cpu) else None,
+        "cpu_baseline": cpu_baseline(args.cpu_seconds) if (args.full and world == 1 and not args.no_cpu) else None,
     }
     print(json.dumps(line), flush=True)
 
@@ -1222,12 +1270,15 @@ def run_dry(args, rank, world, dev):
     from miner_amd import distributed
     total = args.batch or NEWS_B
     start, count = distributed.shard_range(total, rank, world)
-    a = torch.randn(64, 64)
+    a = torch.randn(64, 64, generator=torch.Generator().manual_seed(36))
+    out = [None]
 
     def step(i, timed):
-        torch.mm(a, a)
+        out[0] = torch.mm(a, a)
 
     elapsed = timed_steps(step, args.steps, args.warmup, world, dev)
+    if rank == 0:
+        dump_outputs(args.dump_outputs, {"product": out[0]})
     shards = [(start, count)]
     if world > 1:
         shards = [None] * world
@@ -1264,8 +1315,14 @@ def launch_ranks(n):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=None, help="ranks (one per GPU); default WORLD_SIZE or 1")
-    ap.add_argument("--steps", type=int, default=20)
-    ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--steps", type=int, default=None, help="timed steps (default 20; corpus 5)")
+    ap.add_argument("--warmup", type=int, default=None, help="untimed steps before them (default 5; corpus 1)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline: CPU baselines, the other precisions, "
+                         "configs 2 / 4 / 5, the dense-row and wide sub-lines, the metric step, AUC parity")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned as DIR/<name>.npy (float32 / float64; a seeded "
+                         "row sample when an array is large)")
     ap.add_argument("--workload", default="config3", choices=["config3", "config3-dense", "fastformer", "corpus"])
     ap.add_argument("--batch", type=int, default=None, help="impressions (users) per GPU per step")
     ap.add_argument("--pool", type=int, default=2, help="distinct resident batches per GPU")
@@ -1290,8 +1347,13 @@ def main():
     ap.add_argument("--no-weak", action="store_true", help="N>1: skip the per-GPU 3M weak-scaling sub-field")
     ap.add_argument("--dry-run", action="store_true", help="CPU/gloo: launcher and timing protocol only")
     args = ap.parse_args()
-    args.steps_set = "--steps" in sys.argv
-    args.warmup_set = "--warmup" in sys.argv
+    corpus_run = args.workload == "corpus" and not args.dry_run
+    if args.steps is None:
+        args.steps = 5 if corpus_run else 20
+    if args.warmup is None:
+        args.warmup = 1 if corpus_run else 5
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     env_world = os.environ.get("WORLD_SIZE")
     if env_world is None and args.gpus is not None and args.gpus > 1:

@@ -34,3 +34,37 @@ def test_single_rank_default():
     line = _run("--dry-run", "--steps", "2", "--warmup", "0")
     assert line["n_gpus"] == 1
     assert line["config"]["global_batch"] == 3_000_000
+
+
+def test_dump_outputs_and_full(tmp_path):
+    """--dump-outputs writes the last step's output as float .npy, identical from run to run;
+    --steps sets the timed steps (also as --steps=N) and --full is accepted."""
+    import numpy as np
+    a, b = str(tmp_path / "a"), str(tmp_path / "b")
+    la = _run("--gpus", "1", "--dry-run", "--steps=4", "--warmup", "1", "--dump-outputs", a)
+    lb = _run("--gpus", "1", "--dry-run", "--steps", "2", "--warmup", "0", "--full", "--dump-outputs", b)
+    assert la["steps"] == 4 and la["warmup"] == 1 and lb["steps"] == 2 and lb["warmup"] == 0
+    assert la["ms_per_step"] > 0 and lb["ms_per_step"] > 0
+    assert os.listdir(a) == ["product.npy"] == os.listdir(b)
+    xa, xb = np.load(os.path.join(a, "product.npy")), np.load(os.path.join(b, "product.npy"))
+    assert xa.dtype == np.float32 and xa.shape == (64, 64) and np.isfinite(xa).all()
+    assert np.array_equal(xa, xb)
+
+
+def test_dump_outputs_samples_large_arrays(tmp_path):
+    """An array past its share of the 64 MB cap is written as the same seeded rows, in row order."""
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    big = torch.arange(3_000_000, dtype=torch.float32)[:, None].expand(-1, 40)      # 480 MB if written whole
+    idx = torch.arange(1000, dtype=torch.int64).reshape(10, 100)
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), {"scores": big, "index": idx})
+    sa, sb = np.load(tmp_path / "a" / "scores.npy"), np.load(tmp_path / "b" / "scores.npy")
+    assert sa.dtype == np.float32 and sa.shape[1] == 40 and 100_000 < sa.shape[0] < 3_000_000
+    assert np.array_equal(sa, sb) and (np.diff(sa[:, 0]) > 0).all() and (sa == sa[:, :1]).all()
+    ia = np.load(tmp_path / "a" / "index.npy")
+    assert ia.dtype == np.float64 and np.array_equal(ia, idx.numpy())
+    total = sum(os.path.getsize(tmp_path / "a" / f) for f in os.listdir(tmp_path / "a"))
+    assert total <= 64 * 1000 * 1000

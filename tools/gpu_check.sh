@@ -13,5 +13,5 @@ timeout -k 10 900 python3 -u -m pytest tests -m gpu ${K:+-k "$K"} --maxfail 25 -
 tail -3 "$O/gpu_tests.log"
 timeout -k 10 300 python3 -c "import __graft_entry__ as g; g.smoke()" > "$O/smoke.log" 2>&1 || { tail -20 "$O/smoke.log"; exit 1; }
 cat "$O/smoke.log"
-timeout -k 10 600 python3 bench.py > "$O/bench.json" 2> "$O/bench.err" || { tail -20 "$O/bench.err"; exit 1; }
+timeout -k 10 600 python3 bench.py --full > "$O/bench.json" 2> "$O/bench.err" || { tail -20 "$O/bench.err"; exit 1; }
 cat "$O/bench.json"

@@ -13,7 +13,7 @@ mkdir -p "$O"
 cd /tmp && export TMPDIR=/tmp
 echo "[profile] kernel trace of the bench"
 timeout -k 10 400 rocprofv3 --kernel-trace --stats -d "$O/trace" -o run --output-format csv -- \
-  python3 "$R/bench.py" > "$O/bench_traced.json" 2> "$O/trace.err"
+  python3 "$R/bench.py" --full > "$O/bench_traced.json" 2> "$O/trace.err"
 find "$O/trace" -name '*kernel_stats.csv' -exec cp {} "$O/kernel_stats.csv" \; -quit
 for DT in fp32 bf16; do
   i=0
@@ -31,7 +31,7 @@ python3 "$R/tools/pmc_traffic.py" --news32 --batch "$B" "$O"/fp32_p* > "$O/traff
 python3 "$R/tools/pmc_traffic.py" --news --batch "$B" "$O"/bf16_p* > "$O/traffic_bf16.txt"
 cp "$R/profiles/pmc_traffic_news_fp32.json" "$R/profiles/pmc_traffic_news.json" "$O/"
 echo "[profile] bench"
-timeout -k 10 400 python3 "$R/bench.py" > "$O/bench.json" 2> "$O/bench.err"
+timeout -k 10 400 python3 "$R/bench.py" --full > "$O/bench.json" 2> "$O/bench.err"
 cat "$O/bench.json"
 find "$O" -type f -size +4M -print -delete
 echo "[profile] done"

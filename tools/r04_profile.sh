@@ -12,7 +12,7 @@ mkdir -p "$O"
 cd /tmp && export TMPDIR=/tmp
 echo "[profile] kernel trace of the bench"
 timeout -k 10 500 rocprofv3 --kernel-trace --stats -d "$O/trace" -o run --output-format csv -- \
-  python3 "$R/bench.py" > "$O/bench_traced.json" 2> "$O/trace.err"
+  python3 "$R/bench.py" --full > "$O/bench_traced.json" 2> "$O/trace.err"
 find "$O/trace" -name '*kernel_stats.csv' -exec cp {} "$O/kernel_stats.csv" \; -quit
 python3 "$R/tools/trace_split.py" "$(find "$O/trace" -name '*kernel_trace.csv' | head -1)" > "$O/headline_trace_split.json"
 SQ1="SQ_WAVES SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS"
@@ -49,7 +49,7 @@ python3 "$P" --batch 50000 --tag news_scoreIDF16bLi0ELb0ELi3ELi64ELi4ELi1E --tag
   --out "$R/profiles/pmc_traffic_news_c2.json" "$O"/c2bf16_p* > "$O/traffic_c2bf16.txt"
 cp "$R"/profiles/pmc_traffic_news*.json "$O/"
 echo "[profile] bench"
-timeout -k 10 400 python3 "$R/bench.py" > "$O/bench.json" 2> "$O/bench.err"
+timeout -k 10 400 python3 "$R/bench.py" --full > "$O/bench.json" 2> "$O/bench.err"
 cat "$O/bench.json"
 find "$O" -type f -size +4M -print -delete
 echo "[profile] done"

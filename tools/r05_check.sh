@@ -14,7 +14,7 @@ if [ "$TESTS" = "1" ]; then
   if [ $rc -ne 0 ]; then grep -E "FAILED|ERROR|Fatal|Abort" "$O/gpu_tests.log" | head -40; [ $rc -ge 124 ] && exit $rc; fi
   timeout -k 10 300 python3 -c "import __graft_entry__ as g; g.smoke()" > "$O/smoke.log" 2>&1 || { tail -20 "$O/smoke.log"; exit 1; }
   tail -2 "$O/smoke.log"
-  timeout -k 10 600 python3 bench.py > "$O/bench.json" 2> "$O/bench.err" || { tail -20 "$O/bench.err"; exit 1; }
+  timeout -k 10 600 python3 bench.py --full > "$O/bench.json" 2> "$O/bench.err" || { tail -20 "$O/bench.err"; exit 1; }
   python3 -c "import json;d=json.load(open('$O/bench.json'));print('value',d['value'],'kernel_ms',d['roofline']['kernel_ms'],'frac',d['roofline']['frac'])"
 fi
 if [ "$STAGES" = "1" ]; then

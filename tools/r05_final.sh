@@ -28,7 +28,7 @@ for pass in ${PASSES:+"FETCH_SIZE" "WRITE_SIZE" "$SQ2" "$SQ1"}; do
 done
 [ -n "$PASSES" ] && { python3 "$R/tools/pmc_traffic.py" --batch 3000000 --news32 "$O"/n32_p* > "$O/traffic_news32.txt" || exit 1; }
 echo "[final] bench"
-timeout -k 10 400 python3 "$R/bench.py" > "$O/bench.json" 2> "$O/bench.err" || { tail -20 "$O/bench.err"; exit 1; }
+timeout -k 10 400 python3 "$R/bench.py" --full > "$O/bench.json" 2> "$O/bench.err" || { tail -20 "$O/bench.err"; exit 1; }
 cp "$R"/profiles/pmc_traffic*.json "$O/"
 find "$O" -type f -size +4M -delete
 echo "[final] done"

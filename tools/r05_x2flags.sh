@@ -41,6 +41,6 @@ python3 "$P" --batch 50000 --tag "news_score_x2<0, false, 4, 2, false, false>" \
   --out "$R/profiles/pmc_traffic_news_c2_x2.json" "$O"/c2x2_p* > "$O/traffic_c2x2.txt" || exit 1
 cp "$R"/profiles/pmc_traffic_news_x2.json "$R"/profiles/pmc_traffic_news_x2_full.json "$R"/profiles/pmc_traffic_news_c2_x2.json "$O/"
 echo "[x2f] bench"
-timeout -k 10 400 python3 "$R/bench.py" > "$O/bench.json" 2> "$O/bench.err" || { tail -20 "$O/bench.err"; exit 1; }
+timeout -k 10 400 python3 "$R/bench.py" --full > "$O/bench.json" 2> "$O/bench.err" || { tail -20 "$O/bench.err"; exit 1; }
 find "$O" -type f -size +4M -delete
 echo "[x2f] done"

@@ -9,7 +9,7 @@ mkdir -p "$O"
 if [ "$#" -gt 0 ]; then bash "$R/tools/r06_pmc.sh" "${TAG}_pmc" "$@" || exit 1; fi
 echo "[fin] bench"
 cd "$R"
-timeout -k 10 900 python3 "$R/bench.py" > "$O/bench.json" 2> "$O/bench.err" || { tail -20 "$O/bench.err"; exit 1; }
+timeout -k 10 900 python3 "$R/bench.py" --full > "$O/bench.json" 2> "$O/bench.err" || { tail -20 "$O/bench.err"; exit 1; }
 python3 - "$O/bench.json" <<'PY'
 import json, sys
 t = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])
