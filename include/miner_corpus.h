@@ -14,6 +14,8 @@
  *                             weighted: Σ_k softmax_k(proj_k · e_n) · M_k (model.py:213-214)
  *                             max / mean: max_k / mean_k M_k (model.py:128-131);
  *                             per user the topk best (score desc, news id asc on ties).
+ *   miner_rank_topk_filtered(...)  the same, leaving out a per-user list of news ids (the clicked
+ *                             history) and every news outside a table-wide eligibility bitmap.
  *
  * Conventions are those of miner_score.h. dtype: MINER_DTYPE_F32 (exact fp32, parity mode),
  * MINER_DTYPE_BF16 or MINER_DTYPE_F16 (16-bit operands, fp32 accumulation and softmax).
@@ -79,6 +81,27 @@ int miner_rank_topk_split_recommended(int U);
 int miner_rank_topk_ws(void* stream, int dtype, int score_type, const void* user_mui, const void* user_proj,
                        const void* news, int U, int N, int d, int K, int topk, float* top_scores,
                        int32_t* top_ids, void* workspace, size_t workspace_bytes);
+
+/*
+ * miner_rank_topk_ws with two optional filters on what a user's list may hold (the two calls above
+ * are this one with both NULL). They decide only which (score, id) pairs are kept, inside the
+ * ranker's threshold test; no score changes, and a list with fewer than topk survivors ends in
+ * -inf / -1 entries. Split and unsplit forms agree bit for bit under the filters too.
+ *   exclude_ids [U, E] int32, row-major, 0 <= E <= MINER_CORPUS_MAX_L: news ids that must not
+ *               appear in user u's list (its clicked history, say). Entries outside [0, N) are
+ *               ignored (-1 is the usual padding); duplicates are allowed. E == 0: no exclusion,
+ *               whatever the pointer.
+ *   news_ok     ceil(N / 32) uint32 words, or NULL for "every news": news n may be ranked iff
+ *               bit (n & 31) of word (n >> 5) is set (bit 0 is the least significant). Bits at
+ *               or past N in the last word are never read.
+ * Both are device pointers, 4-byte aligned. Beyond miner_rank_topk_ws's checks: E < 0, or E > 0
+ * with a NULL exclude_ids: MINER_EINVAL; E > MINER_CORPUS_MAX_L: MINER_ESHAPE; a misaligned
+ * filter pointer: MINER_EALIGN (all before any launch).
+ */
+int miner_rank_topk_filtered(void* stream, int dtype, int score_type, const void* user_mui,
+                             const void* user_proj, const void* news, int U, int N, int d, int K, int topk,
+                             const int32_t* exclude_ids, int E, const uint32_t* news_ok,
+                             float* top_scores, int32_t* top_ids, void* workspace, size_t workspace_bytes);
 
 #ifdef __cplusplus
 }

@@ -46,7 +46,7 @@
 extern "C" {
 #endif
 
-#define MINER_ABI_VERSION 5
+#define MINER_ABI_VERSION 6
 
 /* MINER_DTYPE_F16 is accepted by the full-corpus entry points of miner_corpus.h only (config 5).
  * MINER_DTYPE_F32_MFMA (fp32 tensors, every product on the fp32 MFMA) by miner_score,

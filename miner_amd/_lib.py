@@ -16,7 +16,7 @@ LIB_PATH = os.environ.get("MINER_HIP_LIB", os.path.join(_HERE, "libminer_hip.so"
 DTYPE_F32, DTYPE_BF16, DTYPE_F16, DTYPE_F32_MFMA, DTYPE_F32_X6 = 0, 1, 2, 3, 4
 SCORE_WEIGHTED, SCORE_MAX, SCORE_MEAN, SCORE_NONE = 0, 1, 2, 3
 SCORE_TYPES = {"weighted": SCORE_WEIGHTED, "max": SCORE_MAX, "mean": SCORE_MEAN, "none": SCORE_NONE}
-ABI_VERSION = 5
+ABI_VERSION = 6
 
 # every symbol include/*.h declares: name -> (restype, argtypes)
 _P = ctypes.c_void_p
@@ -47,6 +47,8 @@ SIGNATURES = {
     "miner_rank_topk_workspace_bytes": (ctypes.c_size_t, [_I, _I]),
     "miner_rank_topk_split_recommended": (_I, [_I]),
     "miner_rank_topk_ws": (_I, [_P, _I, _I, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, ctypes.c_size_t]),
+    "miner_rank_topk_filtered": (_I, [_P, _I, _I, _P, _P, _P, _I, _I, _I, _I, _I, _P, _I, _P, _P, _P, _P,
+                                      ctypes.c_size_t]),
     # include/miner_news.h
     "miner_news_precompute": (_I, [_P, _I, _P, _I, _P, _I, _I, _I, _P, _P]),
     "miner_score_news": (_I, [_P, _I, _I, _P, _P, _P, _I, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P]),

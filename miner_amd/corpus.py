@@ -4,6 +4,7 @@ d=768, fp16), backed by libminer_hip.so (include/miner_corpus.h).
     packed = pack_encoder(w_poly, context_codes, w_target, dtype=torch.float16)
     mui, proj = encode_users(history, his_mask, packed)                 # or table + his_ids
     top_scores, top_ids = rank_topk(mui, proj, news_table, topk=100)   # never materialises U x N
+    rank_topk(..., exclude_ids=clicked, eligible=fresh)    # per-user "not these", table-wide "only these"
 
 The click score of (user, news) is the reference's (src/model/model.py:127-134, 213-214) with the
 impression's candidate set replaced by the whole news table; ties rank the lower news id first.
@@ -104,10 +105,44 @@ def encode_users(history: Tensor, his_mask: Tensor, packed: EncoderWeights, *, h
     return (mui, proj, m32) if return_f32 else (mui, proj)
 
 
+def _pack_bits(mask: Tensor) -> Tensor:
+    """bool [N] -> int32 [ceil(N/32)]: news n is bit n & 31 (bit 0 least significant) of word n >> 5."""
+    n = mask.shape[0]
+    words = (n + 31) // 32
+    m = torch.zeros(words * 32, dtype=torch.int64, device=mask.device)
+    m[:n] = mask
+    w = (m.view(words, 32) << torch.arange(32, dtype=torch.int64, device=mask.device)).sum(dim=1)
+    return torch.where(w >= 2 ** 31, w - 2 ** 32, w).to(torch.int32)
+
+
+def pack_eligible(mask: Tensor) -> Tensor:
+    """The ranker's eligibility bitmap (include/miner_corpus.h, news_ok) of a bool [N] device tensor:
+    int32 [ceil(N/32)], news n at bit n & 31 of word n >> 5."""
+    _require_device(mask)
+    if mask.dtype != torch.bool or mask.dim() != 1:
+        raise ValueError("eligible mask must be a bool [N] tensor")
+    return _pack_bits(mask)
+
+
+def _eligible_words(eligible: Tensor, N: int) -> Tensor:
+    words = (N + 31) // 32
+    if eligible.dim() == 1 and eligible.dtype == torch.bool and eligible.shape[0] == N:
+        return pack_eligible(eligible)
+    if eligible.dim() == 1 and eligible.dtype == torch.int32 and eligible.shape[0] == words:
+        return eligible.contiguous()
+    raise ValueError(f"eligible must be bool [{N}] or packed int32 [{words}] (pack_eligible)")
+
+
 def rank_topk(user_mui: Tensor, user_proj: Optional[Tensor], news: Tensor, topk: int, *,
-              score_type: str = "weighted"):
+              score_type: str = "weighted", exclude_ids: Optional[Tensor] = None,
+              eligible: Optional[Tensor] = None):
     """Top-k news per user by the click score, best first: (scores [U,topk] fp32, ids [U,topk]
-    int32); entries past the table size are (-inf, -1)."""
+    int32); entries past the table size are (-inf, -1).
+
+    exclude_ids [U,E] (any integer dtype, E <= 256): news ids kept out of user u's list; entries
+    outside [0, N), such as a -1 padding, exclude nothing. eligible: bool [N], or the packed int32
+    [ceil(N/32)] of pack_eligible: only these news are ranked. A list with fewer survivors than
+    topk ends in (-inf, -1) entries; the scores themselves never change."""
     st = _lib.SCORE_TYPES.get(score_type)
     if st is None or st == _lib.SCORE_NONE:
         raise ValueError("Invalid method of aggregating matching score")  # model.py:136
@@ -125,6 +160,17 @@ def rank_topk(user_mui: Tensor, user_proj: Optional[Tensor], news: Tensor, topk:
         raise ValueError("shape mismatch between user vectors and the news table")
     if not 1 <= topk <= MAX_TOPK:
         raise ValueError(f"topk must be in [1, {MAX_TOPK}]")
+    _require_device(exclude_ids, eligible)
+    excl, E = None, 0
+    if exclude_ids is not None:
+        if exclude_ids.dim() != 2 or exclude_ids.shape[0] != U or exclude_ids.is_floating_point() \
+                or exclude_ids.dtype == torch.bool:
+            raise ValueError(f"exclude_ids must be an integer [{U}, E] tensor")
+        E = exclude_ids.shape[1]
+        if E > MAX_L:
+            raise ValueError(f"exclude_ids holds {E} ids per user, more than {MAX_L}")
+        excl = _contig(exclude_ids, torch.int32) if E else None
+    ok = None if eligible is None else _eligible_words(eligible, N)
     dev = mui.device
     top_s = torch.empty(U, topk, dtype=torch.float32, device=dev)
     top_i = torch.empty(U, topk, dtype=torch.int32, device=dev)
@@ -136,25 +182,43 @@ def rank_topk(user_mui: Tensor, user_proj: Optional[Tensor], news: Tensor, topk:
     nws = int(lib.miner_rank_topk_workspace_bytes(U, topk)) if split else 0
     ws = torch.empty(nws, dtype=torch.uint8, device=dev) if nws else None
     with torch.cuda.device(dev):
-        rc = _lib.lib().miner_rank_topk_ws(_stream(dev), dt, st, _ptr(mui), _ptr(proj), _ptr(tab), U, N, d, K, topk,
-                                           _ptr(top_s), _ptr(top_i), _ptr(ws), nws)
+        if excl is None and ok is None:
+            rc = lib.miner_rank_topk_ws(_stream(dev), dt, st, _ptr(mui), _ptr(proj), _ptr(tab), U, N, d, K, topk,
+                                        _ptr(top_s), _ptr(top_i), _ptr(ws), nws)
+        else:
+            rc = lib.miner_rank_topk_filtered(_stream(dev), dt, st, _ptr(mui), _ptr(proj), _ptr(tab), U, N, d, K,
+                                              topk, _ptr(excl), E, _ptr(ok), _ptr(top_s), _ptr(top_i), _ptr(ws), nws)
     _lib.check(rc, "miner_rank_topk")
     return top_s, top_i
 
 
 def rank_corpus(news: Tensor, his_ids: Tensor, his_mask: Tensor, packed: EncoderWeights, topk: int, *,
                 his_bias: Optional[Tensor] = None, score_type: str = "weighted", batch: int = 16384,
-                out: Optional[tuple] = None):
+                out: Optional[tuple] = None, exclude_history: bool = False, exclude_ids: Optional[Tensor] = None,
+                eligible: Optional[Tensor] = None):
     """BASELINE config 5 on one GPU's share of the users: every user (his_ids [U,L] into the news
     table [N,d], his_mask [U,L]) encoded and ranked against the whole table, ``batch`` users per
     encode + rank pair so that the [batch,K,d] user vectors are all that is ever held (125,000 users
     at K = 64, d = 768, fp16 would be 24.6 GB of mui + proj at once). Returns (scores [U,topk] fp32,
     ids [U,topk] int32), best first: each user's list is independent of the batching
-    (tests/test_gpu_fullsize.py). ``out`` = preallocated (scores, ids) to write into."""
+    (tests/test_gpu_fullsize.py). ``out`` = preallocated (scores, ids) to write into.
+
+    ``exclude_history`` keeps each user's own clicked news (the unmasked his_ids) out of its list,
+    ``exclude_ids`` [U,E] further ids, together at most 256 per user; ``eligible`` as in rank_topk."""
     if batch <= 0:
         raise ValueError("batch must be positive")
     U = his_ids.shape[0]
     dev = news.device
+    _require_device(news, his_ids, his_mask, exclude_ids, eligible)
+    excl = exclude_ids
+    if excl is not None and (excl.dim() != 2 or excl.shape[0] != U):
+        raise ValueError(f"exclude_ids must be [{U}, E]")
+    if exclude_history:
+        seen = torch.where(his_mask.to(torch.bool), his_ids, -1).to(torch.int32)   # padded slots exclude nothing
+        excl = seen if excl is None else torch.cat([seen, excl.to(torch.int32)], dim=1)
+    if excl is not None and excl.shape[1] > MAX_L:
+        raise ValueError(f"{excl.shape[1]} excluded ids per user, more than {MAX_L}")
+    ok = None if eligible is None else _eligible_words(eligible, news.shape[0])   # packed once
     top_s, top_i = out if out is not None else (torch.empty(U, topk, dtype=torch.float32, device=dev),
                                                 torch.empty(U, topk, dtype=torch.int32, device=dev))
     with_proj = score_type == "weighted"
@@ -162,7 +226,8 @@ def rank_corpus(news: Tensor, his_ids: Tensor, his_mask: Tensor, packed: Encoder
         u1 = min(U, u0 + batch)
         mui, proj = encode_users(news, his_mask[u0:u1], packed, his_ids=his_ids[u0:u1],
                                  his_bias=None if his_bias is None else his_bias[u0:u1], with_proj=with_proj)
-        s, i = rank_topk(mui, proj, news, topk, score_type=score_type)
+        s, i = rank_topk(mui, proj, news, topk, score_type=score_type,
+                         exclude_ids=None if excl is None else excl[u0:u1], eligible=ok)
         top_s[u0:u1] = s
         top_i[u0:u1] = i
     return top_s, top_i

@@ -38,6 +38,7 @@ constexpr int kDcT = 8;          // Dc padded to 8 tiles of 32
 constexpr int kMaxD = 768;
 
 inline bool aligned16(const void* q) { return q == nullptr || (reinterpret_cast<uintptr_t>(q) & 15u) == 0; }
+inline bool aligned4(const void* q) { return (reinterpret_cast<uintptr_t>(q) & 3u) == 0; }
 
 int num_cus() {
   static int cus = 0;
@@ -446,7 +447,9 @@ struct RkParams {
   float* ws_s;             // S > 1: per (user, news slice) top-k lists [U][S][topk], merged by rk_merge
   int32_t* ws_i;
   size_t ws_bytes;         // the caller's workspace size (the split form needs U·S·topk·8)
-  int U, N, d, K, topk, score_type;
+  const int32_t* excl;     // [U][E] news ids a user's list must not hold (NULL / E = 0: none)
+  const uint32_t* ok;      // ceil(N / 32) words, bit n & 31 of word n >> 5: news n may be ranked (NULL: all)
+  int U, N, d, K, topk, score_type, E;
 };
 
 // S > 1 (S = 8, grid = 256): the news steps are dealt to S slices (step st of slice s is news step
@@ -502,24 +505,27 @@ template <int GEO> constexpr int kRing = GEO ? 4 : 2;
 // total order of ranked entries: higher score first, then lower news id
 __device__ __forceinline__ bool better(float s, int i, float s2, int i2) { return s > s2 || (s == s2 && i < i2); }
 
-template <int NR, int GEO = 0>
+template <int NR, int GEO = 0, bool FLT = false>
 struct RkLds {
   static constexpr int kARows = kUT * NR * 32;
   static constexpr int kStage = (kARows + kNT) * kRB<GEO>;
   static constexpr int kOffList = kRing<GEO> * kStage;              // [kUT][kMaxTopk] float + int
   static constexpr int kOffStage = kOffList + kUT * kMaxTopk * 8;  // staged candidates [2 bufs][kUT][kNT]
   static constexpr int kOffCnt = kOffStage + 2 * kUT * kNT * 8;     // list counts [kUT], staged [2][kUT]
-  static constexpr int kTotal = kOffCnt + 64;
+  static constexpr int kOffExcl = kOffCnt + 64;                     // the tile's exclusion lists [kUT][kMaxL] int
+  static constexpr int kTotal = kOffExcl + (FLT ? kUT * kMaxL * 4 : 0);
 };
 
-// NCH: RB-byte d-chunks per row (0: at run time); GEO: the stream geometry (kRB / kRing)
-template <class T, int NKT, int SCORE, int NCH = 0, int S = 1, int GEO = 0, int KC = 0>   // KC: K compile-time (0: run time)
+// NCH: RB-byte d-chunks per row (0: at run time); GEO: the stream geometry (kRB / kRing); FLT: the
+// filtered form (RkParams excl / ok). A compile-time switch: as run-time branches on the two pointers
+// the unfiltered config-5 step measured 79.5 against the parent's 76.0 ms (profiles/rk_filter_ab.txt).
+template <class T, int NKT, int SCORE, int NCH = 0, int S = 1, int GEO = 0, int KC = 0, bool FLT = false>   // KC: K compile-time (0: run time)
 __global__ __launch_bounds__(kThreads) void rk_fused(RkParams p) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   constexpr bool kW = SCORE == MINER_SCORE_WEIGHTED;
   constexpr int NR = kW ? 2 * NKT : NKT;            // row tiles per user: mui (and proj)
   constexpr int RB = kRB<GEO>, RING = kRing<GEO>, PD = RING - 1;   // PD: chunks in flight
-  using LD = RkLds<NR, GEO>;
+  using LD = RkLds<NR, GEO, FLT>;
   constexpr int kChunkSlabs = RB / (32 * (int)sizeof(T));          // 32-index slabs per chunk
   static_assert(kChunkSlabs >= 1, "a chunk holds whole slabs");
   const int d = NCH > 0 ? NCH * RB / (int)sizeof(T) : p.d, K = KC > 0 ? KC : p.K, N = p.N;
@@ -533,6 +539,8 @@ __global__ __launch_bounds__(kThreads) void rk_fused(RkParams p) {
   float* stg_s = reinterpret_cast<float*>(smem + LD::kOffStage);                    // [buf][uu][kNT]
   int* stg_i = reinterpret_cast<int*>(smem + LD::kOffStage + 2 * kUT * kNT * 4);
   int* cnt = reinterpret_cast<int*>(smem + LD::kOffCnt);   // [0, kUT) list sizes, kUT + buf * kUT + uu staged
+  int* excl = reinterpret_cast<int*>(smem + LD::kOffExcl);  // [kUT][kMaxL], -1 past E (FLT and p.E > 0 only)
+  static_assert(kUT * kMaxL == kThreads && kMaxL == 4 * 64, "one exclusion slot per thread, four per lane of a wave");
   // the user's merging wave: 0 and 5 (two SIMDs under the wave -> SIMD w % 4 placement)
   const bool merger = wave == 5 * uu;
   const T* __restrict__ mui = static_cast<const T*>(p.mui);
@@ -679,6 +687,12 @@ __global__ __launch_bounds__(kThreads) void rk_fused(RkParams p) {
   }
   int q = 0;
   for (int ti = first; ti < ntiles; ti += tstride) {
+    // the tile's exclusion lists (the previous tile's epilogues are behind its closing barriers; this
+    // tile's first epilogue comes after a chunk barrier). A user past U and slots past E hold -1.
+    if (FLT && p.E > 0) {
+      const int eu = ti * kUT + (int)(threadIdx.x / kMaxL), es = threadIdx.x % kMaxL;
+      excl[threadIdx.x] = eu < p.U && es < p.E ? p.excl[(size_t)eu * p.E + es] : -1;
+    }
     for (int sl = 0; sl < nsteps; ++sl) {
       const int st = news_step(sl);
       f32x16 acc[NR][2];
@@ -788,8 +802,33 @@ __global__ __launch_bounds__(kThreads) void rk_fused(RkParams p) {
                 if (32 * kt + 16 * h + e < K) sm += acc[kt][nt][e];
             score = xor32_sum(sm) / (float)K;            // model.py:130-131
           }
-          const bool cand = h == 0 && n < N && user < p.U && better(score, n, th_s, th_i);
-          const unsigned long long bal = __ballot(cand);
+          bool cand = h == 0 && n < N && user < p.U && better(score, n, th_s, th_i);
+          unsigned long long bal = __ballot(cand);
+          // the filters, on the few half-waves with an entry past the threshold: the eligibility
+          // word of these 32 news (one per (step, nsub, nt); a candidate has n < N, so the word is
+          // inside the bitmap), then the user's exclusion list, four slots per lane, against the n of
+          // each candidate lane in turn (bal is wave-uniform; usually one or two bits)
+          if constexpr (FLT) {
+            if (bal) {
+              const int n0 = st * kNT + 64 * nsub + 32 * nt;
+              if (p.ok != nullptr) {
+                cand = cand && ((p.ok[n0 >> 5] >> r) & 1u);
+                bal = __ballot(cand);
+              }
+              if (p.E > 0 && bal) {
+                const int* ex = excl + uu * kMaxL + lane;
+                const int x0 = ex[0], x1 = ex[64], x2 = ex[128], x3 = ex[192];
+                unsigned long long hit = 0;
+                for (unsigned long long rem = bal; rem; rem &= rem - 1) {
+                  const int j = __builtin_ctzll(rem);             // lane j < 32 holds news n0 + j
+                  const int nj = n0 + j;
+                  if (__ballot(x0 == nj || x1 == nj || x2 == nj || x3 == nj)) hit |= 1ull << j;
+                }
+                cand = cand && !((hit >> lane) & 1);
+                bal &= ~hit;
+              }
+            }
+          }
           if (bal) {
             const int buf = sl & 1;
             int b0 = 0;
@@ -926,24 +965,24 @@ bool rk_split(const RkParams& prm) {
   return num_cus() == 256;
 }
 
-template <class T, int NKT, int S, int GEO>
+template <class T, int NKT, int S, int GEO, bool FLT>
 int rk_launch_geo(void* stream, const RkParams& prm, bool split) {
   // d = 768 in 16-bit (config 5): the chunk count compile-time
-  void (*kern)(RkParams) = split ? rk_fused<T, NKT, S, 0, kSplit, GEO> : rk_fused<T, NKT, S, 0, 1, GEO>;
+  void (*kern)(RkParams) = split ? rk_fused<T, NKT, S, 0, kSplit, GEO, 0, FLT> : rk_fused<T, NKT, S, 0, 1, GEO, 0, FLT>;
   if constexpr (sizeof(T) == 2) {
     // config 5's d = 768 and K = 64 compile-time (the masked interest loops of the epilogue compile
     // away; the top-k equals the oracle's at the 16-bit bar, tests/test_gpu_corpus.py)
     constexpr int kN768 = 768 * 2 / kRB<GEO>;
     if (prm.d == 768) {
       if (NKT == 2 && prm.K == 64)
-        kern = split ? rk_fused<T, NKT, S, kN768, kSplit, GEO, 64> : rk_fused<T, NKT, S, kN768, 1, GEO, 64>;
+        kern = split ? rk_fused<T, NKT, S, kN768, kSplit, GEO, 64, FLT> : rk_fused<T, NKT, S, kN768, 1, GEO, 64, FLT>;
       else
-        kern = split ? rk_fused<T, NKT, S, kN768, kSplit, GEO> : rk_fused<T, NKT, S, kN768, 1, GEO>;
+        kern = split ? rk_fused<T, NKT, S, kN768, kSplit, GEO, 0, FLT> : rk_fused<T, NKT, S, kN768, 1, GEO, 0, FLT>;
     }
   }
   constexpr int NR = S == MINER_SCORE_WEIGHTED ? 2 * NKT : NKT;
-  const int lds = RkLds<NR, GEO>::kTotal;
-  static_assert(RkLds<NR, GEO>::kTotal <= 160 * 1024, "ranker LDS");
+  const int lds = RkLds<NR, GEO, FLT>::kTotal;
+  static_assert(RkLds<NR, GEO, true>::kTotal <= 160 * 1024, "ranker LDS (with the exclusion lists)");
   hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
   if (e != hipSuccess) return (int)e;
   const int ntiles = (prm.U + kUT - 1) / kUT;
@@ -962,14 +1001,16 @@ int rk_launch_geo(void* stream, const RkParams& prm, bool split) {
 template <class T, int NKT, int S>
 int rk_launch(void* stream, const RkParams& prm) {
   const bool split = rk_split(prm);
+  const bool flt = prm.ok != nullptr || prm.E > 0;     // the filtered instantiation only when asked for
   // (GEO 1 — 64-byte rows through a 4-stage ring, three chunks in flight instead of one — measured
   // slower: 95.9 vs 89.7 ms per config-5 step, twice the barriers for no gain in the gather rate;
   // diagnostic builds with -DMINER_RK_GEO1 launch it)
 #ifdef MINER_RK_GEO1
   constexpr int NR = S == MINER_SCORE_WEIGHTED ? 2 * NKT : NKT;
-  if constexpr (sizeof(T) == 2 && NR >= 2) return rk_launch_geo<T, NKT, S, 1>(stream, prm, split);
+  if constexpr (sizeof(T) == 2 && NR >= 2)
+    return flt ? rk_launch_geo<T, NKT, S, 1, true>(stream, prm, split) : rk_launch_geo<T, NKT, S, 1, false>(stream, prm, split);
 #endif
-  return rk_launch_geo<T, NKT, S, 0>(stream, prm, split);
+  return flt ? rk_launch_geo<T, NKT, S, 0, true>(stream, prm, split) : rk_launch_geo<T, NKT, S, 0, false>(stream, prm, split);
 }
 
 template <class T>
@@ -1063,6 +1104,14 @@ int miner_rank_topk(void* stream, int dtype, int score_type, const void* user_mu
 int miner_rank_topk_ws(void* stream, int dtype, int score_type, const void* user_mui, const void* user_proj,
                        const void* news, int U, int N, int d, int K, int topk, float* top_scores, int32_t* top_ids,
                        void* workspace, size_t workspace_bytes) {
+  return miner_rank_topk_filtered(stream, dtype, score_type, user_mui, user_proj, news, U, N, d, K, topk, nullptr, 0,
+                                  nullptr, top_scores, top_ids, workspace, workspace_bytes);
+}
+
+int miner_rank_topk_filtered(void* stream, int dtype, int score_type, const void* user_mui, const void* user_proj,
+                             const void* news, int U, int N, int d, int K, int topk, const int32_t* exclude_ids, int E,
+                             const uint32_t* news_ok, float* top_scores, int32_t* top_ids, void* workspace,
+                             size_t workspace_bytes) {
   const int ck = check_dims(dtype, d, 1, K);
   if (ck != MINER_OK) return ck;
   if (score_type < MINER_SCORE_WEIGHTED || score_type > MINER_SCORE_MEAN) return MINER_EINVAL;
@@ -1071,6 +1120,9 @@ int miner_rank_topk_ws(void* stream, int dtype, int score_type, const void* user
   if (!user_mui || !news || !top_scores || !top_ids) return MINER_EINVAL;
   if (score_type == MINER_SCORE_WEIGHTED && !user_proj) return MINER_EINVAL;
   if (!aligned16(user_mui) || !aligned16(user_proj) || !aligned16(news)) return MINER_EALIGN;
+  if (E < 0 || (E > 0 && !exclude_ids)) return MINER_EINVAL;
+  if (E > kMaxL) return MINER_ESHAPE;
+  if (!aligned4(exclude_ids) || !aligned4(news_ok)) return MINER_EALIGN;
   if (U == 0) return MINER_OK;
   RkParams prm{};
   if (!aligned16(workspace)) return MINER_EALIGN;
@@ -1081,6 +1133,7 @@ int miner_rank_topk_ws(void* stream, int dtype, int score_type, const void* user
     prm.ws_i = reinterpret_cast<int32_t*>(static_cast<char*>(workspace) + (size_t)U * kSplit * topk * 4);
   }
   prm.U = U; prm.N = N; prm.d = d; prm.K = K; prm.topk = topk; prm.score_type = score_type;
+  prm.excl = E > 0 ? exclude_ids : nullptr; prm.E = E; prm.ok = news_ok;
   if (dtype == MINER_DTYPE_BF16) return rk_dispatch<__bf16>(stream, prm);
   if (dtype == MINER_DTYPE_F16) return rk_dispatch<_Float16>(stream, prm);
   return rk_dispatch<float>(stream, prm);
