@@ -16,6 +16,9 @@
  *                             per user the topk best (score desc, news id asc on ties).
  *   miner_rank_topk_filtered(...)  the same, leaving out a per-user list of news ids (the clicked
  *                             history) and every news outside a table-wide eligibility bitmap.
+ *   miner_rank_topk_subset(...)    the same over the table rows of an id list only (cost by the
+ *                             list's length), and miner_topk_merge(...) to fold its lists into
+ *                             lists ranked earlier: incremental ranking of a changing corpus.
  *
  * Conventions are those of miner_score.h. dtype: MINER_DTYPE_F32 (exact fp32, parity mode),
  * MINER_DTYPE_BF16 or MINER_DTYPE_F16 (16-bit operands, fp32 accumulation and softmax).
@@ -102,6 +105,47 @@ int miner_rank_topk_filtered(void* stream, int dtype, int score_type, const void
                              const void* user_proj, const void* news, int U, int N, int d, int K, int topk,
                              const int32_t* exclude_ids, int E, const uint32_t* news_ok,
                              float* top_scores, int32_t* top_ids, void* workspace, size_t workspace_bytes);
+
+/*
+ * miner_rank_topk_filtered over a subset of the table given as an id list: only the rows
+ * news[news_ids[0 .. M)] are fetched and multiplied, so the cost follows M, not N (the bitmap form
+ * streams all N rows whatever the bitmap holds).
+ *   news_ids    [M] int32 device pointer, 4-byte aligned: distinct table rows, in any order (the
+ *               list does not depend on it; ascending ids gather neighbouring rows together).
+ *               Distinctness is a precondition: a repeated id may appear twice in a list. Ids
+ *               outside [0, N) are never ranked and no row is read for them.
+ * The result equals miner_rank_topk_filtered's on the same inputs with news_ok replaced by
+ * news_ok AND "n is in news_ids" — scores and ids bit for bit, split and unsplit forms, every dtype
+ * and score type; ids are table ids, ties rank the lower id first. exclude_ids and news_ok (either
+ * may be NULL) apply to the table id. M == 0 writes (-inf, -1) everywhere without a ranker launch.
+ * After miner_rank_topk_filtered's checks, in its order and with its codes: M < 0, or M > 0 with a
+ * NULL news_ids: MINER_EINVAL; a misaligned news_ids: MINER_EALIGN (all before any launch).
+ */
+int miner_rank_topk_subset(void* stream, int dtype, int score_type, const void* user_mui,
+                           const void* user_proj, const void* news, int U, int N, int d, int K, int topk,
+                           const int32_t* exclude_ids, int E, const uint32_t* news_ok,
+                           const int32_t* news_ids, int M, float* top_scores, int32_t* top_ids,
+                           void* workspace, size_t workspace_bytes);
+
+/*
+ * Merge two per-user lists under the ranker's total order (score desc, news id asc):
+ *   a_scores / a_ids [U, ka], b_scores / b_ids [U, kb], 0 <= ka, kb <= MINER_CORPUS_MAX_TOPK, each
+ *   row a set of (score, id) pairs in any order, an entry with id < 0 (the (-inf, -1) tail of a
+ *   ranked list) holding nothing; within one row the valid ids are distinct.
+ *   out_scores / out_ids [U, topk], topk <= MINER_CORPUS_MAX_TOPK, distinct from the inputs: the
+ *   best topk entries of the union, best first, then (-inf, -1). An id in both rows keeps b's
+ *   entry (a fresh score replaces a stale one).
+ *   news_ok     NULL, or the eligibility bitmap of miner_rank_topk_filtered over N news: entries
+ *               whose bit is clear, or whose id is at or past N, drop out (N is read only then).
+ * With miner_rank_topk_subset this is the incremental update: rank the fresh ids, merge the lists
+ * into the served ones — for disjoint id sets the result is the list of ranking their union, bit for
+ * bit. Device pointers, 4-byte aligned. Negative U / ka / kb, topk <= 0, a NULL pointer where
+ * entries are expected, a bitmap with N <= 0: MINER_EINVAL; ka, kb or topk past the cap:
+ * MINER_ESHAPE; a misaligned pointer: MINER_EALIGN (all before any launch).
+ */
+int miner_topk_merge(void* stream, const float* a_scores, const int32_t* a_ids, int ka, const float* b_scores,
+                     const int32_t* b_ids, int kb, int U, int topk, const uint32_t* news_ok, int N,
+                     float* out_scores, int32_t* out_ids);
 
 #ifdef __cplusplus
 }

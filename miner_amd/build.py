@@ -118,18 +118,22 @@ def build_library(force: bool = False, verbose: bool = False, debug: bool = Fals
 
 
 ASAN_DRIVER = os.path.join(ROOT, "tests", "native", "abi_errors.cpp")
+ASAN_DRIVER_SUBSET = os.path.join(ROOT, "tests", "native", "abi_errors_subset.cpp")
 
 
-def build_asan_driver(force: bool = False, verbose: bool = False) -> str:
+def build_asan_driver(force: bool = False, verbose: bool = False, driver: str = ASAN_DRIVER) -> str:
     """Every csrc/*.hip with AddressSanitizer on its HOST code (``-Xarch_host -fsanitize=address``;
     the gfx950 device code is built as usual and never runs), linked with
     tests/native/abi_errors.cpp into build/asan/abi_errors: a CPU program that drives the
     argument-error paths of every C-ABI entry point (SURVEY §5 sanitizer builds; run by
-    tests/test_asan_abi.py). GPU-side sanitizers are not available on this pool."""
+    tests/test_asan_abi.py). GPU-side sanitizers are not available on this pool.
+
+    ``driver``: another stand-alone driver under tests/native/ (its own main), built the same way
+    into build/asan/<its name>; the library's objects there are shared between the drivers."""
     from concurrent.futures import ThreadPoolExecutor
     od = os.path.join(ROOT, "build", "asan")
-    exe = os.path.join(od, "abi_errors")
-    deps = SOURCES + HEADERS + [ASAN_DRIVER]
+    exe = os.path.join(od, os.path.splitext(os.path.basename(driver))[0])
+    deps = SOURCES + HEADERS + [driver]
     if not force and os.path.exists(exe) and all(os.path.getmtime(exe) >= os.path.getmtime(p) for p in deps):
         return exe
     os.makedirs(od, exist_ok=True)
@@ -151,7 +155,7 @@ def build_asan_driver(force: bool = False, verbose: bool = False) -> str:
         return obj
 
     with ThreadPoolExecutor(min(len(SOURCES) + 1, max(1, (os.cpu_count() or 4) // 2))) as ex:
-        objs = list(ex.map(compile_one, SOURCES + [ASAN_DRIVER]))
+        objs = list(ex.map(compile_one, SOURCES + [driver]))
     cmd = [hipcc(), f"--offload-arch={ARCH}", "-fsanitize=address", *objs, "-o", exe + ".tmp"]
     res = subprocess.run(cmd, capture_output=True, text=True)
     if res.returncode != 0:
@@ -160,8 +164,15 @@ def build_asan_driver(force: bool = False, verbose: bool = False) -> str:
     return exe
 
 
+def build_asan_driver_subset(force: bool = False, verbose: bool = False) -> str:
+    """build/asan/abi_errors_subset: the error paths of miner_rank_topk_subset and miner_topk_merge
+    (tests/native/abi_errors_subset.cpp; run by tests/test_corpus_subset_host.py)."""
+    return build_asan_driver(force=force, verbose=verbose, driver=ASAN_DRIVER_SUBSET)
+
+
 if __name__ == "__main__":
     if "--asan" in sys.argv:
         print(build_asan_driver(force="--force" in sys.argv, verbose=True))
+        print(build_asan_driver_subset(verbose=True))
     else:
         print(build_library(force="--force" in sys.argv, verbose=True, debug="--debug" in sys.argv))

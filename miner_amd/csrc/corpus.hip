@@ -450,6 +450,8 @@ struct RkParams {
   const int32_t* excl;     // [U][E] news ids a user's list must not hold (NULL / E = 0: none)
   const uint32_t* ok;      // ceil(N / 32) words, bit n & 31 of word n >> 5: news n may be ranked (NULL: all)
   int U, N, d, K, topk, score_type, E;
+  const int32_t* ids;      // SUB: the news rows to rank, news[ids[pos]] for pos in [0, M); distinct ids
+  int M;
 };
 
 // S > 1 (S = 8, grid = 256): the news steps are dealt to S slices (step st of slice s is news step
@@ -519,8 +521,15 @@ struct RkLds {
 // NCH: RB-byte d-chunks per row (0: at run time); GEO: the stream geometry (kRB / kRing); FLT: the
 // filtered form (RkParams excl / ok). A compile-time switch: as run-time branches on the two pointers
 // the unfiltered config-5 step measured 79.5 against the parent's 76.0 ms (profiles/rk_filter_ab.txt).
-template <class T, int NKT, int SCORE, int NCH = 0, int S = 1, int GEO = 0, int KC = 0, bool FLT = false>   // KC: K compile-time (0: run time)
+// SUB: the subset form (RkParams ids / M; always with FLT, either filter may be null). The news
+// steps, slices and tiles run over the positions pos in [0, M) of the id list; the row of position
+// pos is news[ids[pos]], gathered with one address per lane; a candidate's identity — in the
+// threshold test, the filters and the staged entry — is its table id ids[pos], so the list does not
+// depend on the order of the ids.
+template <class T, int NKT, int SCORE, int NCH = 0, int S = 1, int GEO = 0, int KC = 0, bool FLT = false,   // KC: K compile-time (0: run time)
+          bool SUB = false>
 __global__ __launch_bounds__(kThreads) void rk_fused(RkParams p) {
+  static_assert(!SUB || (FLT && GEO == 0), "the subset form: a filtered form with one chunk in flight");
   extern __shared__ __attribute__((aligned(16))) char smem[];
   constexpr bool kW = SCORE == MINER_SCORE_WEIGHTED;
   constexpr int NR = kW ? 2 * NKT : NKT;            // row tiles per user: mui (and proj)
@@ -530,7 +539,8 @@ __global__ __launch_bounds__(kThreads) void rk_fused(RkParams p) {
   static_assert(kChunkSlabs >= 1, "a chunk holds whole slabs");
   const int d = NCH > 0 ? NCH * RB / (int)sizeof(T) : p.d, K = KC > 0 ? KC : p.K, N = p.N;
   const int nchunk = NCH > 0 ? NCH : d * (int)sizeof(T) / RB;
-  const int nsteps = ((N + kNT - 1) / kNT + S - 1) / S;            // news steps per slice
+  const int NP = SUB ? p.M : N;                                    // news positions: table rows, or list entries
+  const int nsteps = ((NP + kNT - 1) / kNT + S - 1) / S;           // news steps per slice
   const int ntiles = (p.U + kUT - 1) / kUT;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int uu = wave >> 2, nsub = wave & 3;
@@ -575,12 +585,40 @@ __global__ __launch_bounds__(kThreads) void rk_fused(RkParams p) {
     if (jj < kAJ) {
       const int k = min(32 * (((row >> 5) % NR) % NKT) + (row & 31), K - 1);
       voff[jj] = (uint32_t)(k * d) * (uint32_t)sizeof(T) + cl * 16;
+    } else if constexpr (SUB) {
+      voff[jj] = cl * 16;                                            // the row comes from the id list
     } else {
       voff[jj] = (uint32_t)((row - LD::kARows) * d) * (uint32_t)sizeof(T) + cl * 16;
     }
   }
   // the next chunk to issue: (tile nti, slice step nsl, chunk nc), advanced after each issue
   int nti = first, nsl = 0, nc = 0;
+  // SUB: the table rows of this lane's news blocks in the issue pointer's step nsl (not the step
+  // being computed: the issue side runs PD chunks ahead, across step and tile boundaries), loaded
+  // when nsl moves. Positions at or past M take the list's last entry, and an id is clamped into
+  // [0, N) before it becomes an address (neither is ever a candidate, see the epilogue).
+  int bid[SUB ? kJ : 1];
+  auto load_bids = [&]() {
+    if constexpr (SUB) {
+      const int lane = fresh_lane();
+      const int st = S == 1 ? nsl : slice + S * nsl;
+#pragma unroll
+      for (int jj = kAJ; jj < kJ; ++jj) {
+        const int row = ((wave + kWaves * jj) * 64 + lane) / kUnits;
+        const int pos = min(st * kNT + (row - LD::kARows), p.M - 1);
+        bid[jj] = min(max(p.ids[pos], 0), N - 1);
+      }
+    }
+  };
+  // the id registers' loads complete here, behind a wait the caller has just made (the compiler's
+  // own wait before their first use would otherwise land behind freshly issued DMAs)
+  auto pin_bids = [&]() {
+    if constexpr (SUB) {
+#pragma unroll
+      for (int jj = kAJ; jj < kJ; ++jj) asm volatile("" : "+v"(bid[jj]));
+    }
+  };
+  load_bids();
   auto dma_block = [&](int jj, int stage) {
     const unsigned la = __builtin_amdgcn_readfirstlane(lds_offset(smem + stage * LD::kStage + (wave + kWaves * jj) * 1024));
     if (jj < kAJ) {
@@ -589,6 +627,10 @@ __global__ __launch_bounds__(kThreads) void rk_fused(RkParams p) {
       const int user = min(nti * kUT + ou, p.U - 1);
       const T* src = (kW && t >= NKT) ? proj : mui;
       rk_dma(voff[jj], reinterpret_cast<const char*>(src + (size_t)user * K * d) + nc * RB, la);
+    } else if constexpr (SUB) {
+      // one 64-bit address per lane: the table row of this lane's position, chunk nc, unit voff
+      const char* row = reinterpret_cast<const char*>(news) + (size_t)bid[jj] * ((size_t)d * sizeof(T));
+      dma_b128_rt(row + nc * RB + voff[jj], la);
     } else {
       const int st = news_step(nsl);
       if (st * kNT + kNT <= N) {
@@ -606,6 +648,7 @@ __global__ __launch_bounds__(kThreads) void rk_fused(RkParams p) {
     if (++nc == nchunk) {
       nc = 0;
       if (++nsl == nsteps) { nsl = 0; nti += tstride; }
+      load_bids();
     }
   };
 
@@ -686,6 +729,7 @@ __global__ __launch_bounds__(kThreads) void rk_fused(RkParams p) {
     advance();
   }
   int q = 0;
+  int nid[2] = {-1, -1};       // SUB: the table ids of this lane's news columns in the step being computed
   for (int ti = first; ti < ntiles; ti += tstride) {
     // the tile's exclusion lists (the previous tile's epilogues are behind its closing barriers; this
     // tile's first epilogue comes after a chunk barrier). A user past U and slots past E hold -1.
@@ -706,6 +750,22 @@ __global__ __launch_bounds__(kThreads) void rk_fused(RkParams p) {
           else vm_wait_all();
         }
         if (!(MINER_RK_ABL & 8)) __syncthreads();
+        if constexpr (SUB) {
+          // nothing of this wave is in flight: the id loads of advance() and of the step's first chunk
+          // are complete without a wait of their own. Then, at a step's first chunk, the table ids of
+          // this lane's two news columns, once per step (-1: no candidate).
+          pin_bids();
+          asm volatile("" : "+v"(nid[0]), "+v"(nid[1]));
+          if (c == 0) {
+            const int lane = fresh_lane();
+#pragma unroll
+            for (int nt = 0; nt < 2; ++nt) {
+              const int pos = st * kNT + 64 * nsub + 32 * nt + (lane & 31);
+              const int id = p.ids[min(pos, p.M - 1)];
+              nid[nt] = pos < p.M && (unsigned)id < (unsigned)N ? id : -1;
+            }
+          }
+        }
         // the previous step's staged candidates (its epilogue is behind this barrier); the next
         // epilogue reads the list only after this chunk's barriers
         if (c == 0 && sl > 0 && merger && !(MINER_RK_ABL & 4)) merge((sl - 1) & 1);
@@ -758,7 +818,8 @@ __global__ __launch_bounds__(kThreads) void rk_fused(RkParams p) {
         const int th_i = cnt[uu] < p.topk ? 0x7fffffff : list_i[uu * kMaxTopk + p.topk - 1];
 #pragma unroll
         for (int nt = 0; nt < 2; ++nt) {
-          const int n = st * kNT + 64 * nsub + 32 * nt + r;
+          // the candidate's identity: its table row (SUB: of this position's id, -1 for "none")
+          const int n = SUB ? nid[nt] : st * kNT + 64 * nsub + 32 * nt + r;
           float score;
           if constexpr (kW) {
             // 4 independent max / sum chains per lane (a 32-long dependent chain each otherwise)
@@ -802,7 +863,7 @@ __global__ __launch_bounds__(kThreads) void rk_fused(RkParams p) {
                 if (32 * kt + 16 * h + e < K) sm += acc[kt][nt][e];
             score = xor32_sum(sm) / (float)K;            // model.py:130-131
           }
-          bool cand = h == 0 && n < N && user < p.U && better(score, n, th_s, th_i);
+          bool cand = h == 0 && (SUB ? n >= 0 : n < N) && user < p.U && better(score, n, th_s, th_i);
           unsigned long long bal = __ballot(cand);
           // the filters, on the few half-waves with an entry past the threshold: the eligibility
           // word of these 32 news (one per (step, nsub, nt); a candidate has n < N, so the word is
@@ -812,7 +873,8 @@ __global__ __launch_bounds__(kThreads) void rk_fused(RkParams p) {
             if (bal) {
               const int n0 = st * kNT + 64 * nsub + 32 * nt;
               if (p.ok != nullptr) {
-                cand = cand && ((p.ok[n0 >> 5] >> r) & 1u);
+                if constexpr (SUB) cand = cand && ((p.ok[n >> 5] >> (n & 31)) & 1u);   // per lane: ids are scattered
+                else cand = cand && ((p.ok[n0 >> 5] >> r) & 1u);
                 bal = __ballot(cand);
               }
               if (p.E > 0 && bal) {
@@ -821,7 +883,7 @@ __global__ __launch_bounds__(kThreads) void rk_fused(RkParams p) {
                 unsigned long long hit = 0;
                 for (unsigned long long rem = bal; rem; rem &= rem - 1) {
                   const int j = __builtin_ctzll(rem);             // lane j < 32 holds news n0 + j
-                  const int nj = n0 + j;
+                  const int nj = SUB ? __builtin_amdgcn_readlane(n, j) : n0 + j;
                   if (__ballot(x0 == nj || x1 == nj || x2 == nj || x3 == nj)) hit |= 1ull << j;
                 }
                 cand = cand && !((hit >> lane) & 1);
@@ -924,6 +986,97 @@ __global__ __launch_bounds__(256) void rk_merge(const float* __restrict__ ws_s, 
   }
 }
 
+// Two per-user lists a [ka] and b [kb] (ka, kb <= kMaxTopk; sets of (score, id), any order, valid
+// entries id >= 0) -> the first topk of their union under the ranker's total order, then the
+// (-inf, -1) tail. An id in both lists keeps b's entry; with a bitmap (ok, N) entries whose id is
+// at or past N or whose bit is clear drop out. One wave per user: the entries in LDS (a at slots
+// [0, 256), b at [256, 512), a dropped entry's id -1), eight slots per lane, ranked by counting
+// the entries better than each (equal (score, id) pairs of one list: the lower slot first, so the
+// ranks are distinct whatever the input).
+__global__ __launch_bounds__(64 * kMergeUsers) void topk_merge(const float* __restrict__ a_s, const int32_t* __restrict__ a_i,
+                                                               int ka, const float* __restrict__ b_s,
+                                                               const int32_t* __restrict__ b_i, int kb, int U, int topk,
+                                                               const uint32_t* __restrict__ ok, int N,
+                                                               float* __restrict__ out_s, int32_t* __restrict__ out_i) {
+  constexpr int kSlots = 2 * kMaxTopk, kPer = kSlots / 64;
+  __shared__ float ms[kMergeUsers][kSlots];
+  __shared__ int mi[kMergeUsers][kSlots];
+  const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int user = blockIdx.x * kMergeUsers + w;
+  if (user >= U) return;                   // wave-uniform; no block barrier below
+  float sv[kPer];
+  int id[kPer];
+#pragma unroll
+  for (int t = 0; t < kPer; ++t) {
+    const int e = lane + 64 * t, eb = e - kMaxTopk;
+    sv[t] = -INFINITY;
+    id[t] = -1;
+    if (e < ka) {
+      sv[t] = a_s[(size_t)user * ka + e];
+      id[t] = a_i[(size_t)user * ka + e];
+    } else if (eb >= 0 && eb < kb) {
+      sv[t] = b_s[(size_t)user * kb + eb];
+      id[t] = b_i[(size_t)user * kb + eb];
+    }
+    if (ok != nullptr && id[t] >= 0 && (id[t] >= N || !((ok[id[t] >> 5] >> (id[t] & 31)) & 1u))) id[t] = -1;
+    if (id[t] < 0) id[t] = -1;
+    mi[w][e] = id[t];
+  }
+  __builtin_amdgcn_s_waitcnt(0);
+  __builtin_amdgcn_wave_barrier();
+  // an entry of a whose id b holds gives way to b's
+  for (int j = 0; j < kb; ++j) {
+    const int bj = mi[w][kMaxTopk + j];
+#pragma unroll
+    for (int t = 0; t < kMaxTopk / 64; ++t)
+      if (bj >= 0 && id[t] == bj) id[t] = -1;
+  }
+  __builtin_amdgcn_s_waitcnt(0);
+  __builtin_amdgcn_wave_barrier();
+#pragma unroll
+  for (int t = 0; t < kPer; ++t) {
+    ms[w][lane + 64 * t] = sv[t];
+    mi[w][lane + 64 * t] = id[t];
+  }
+  __builtin_amdgcn_s_waitcnt(0);
+  __builtin_amdgcn_wave_barrier();
+  int rank[kPer];
+#pragma unroll
+  for (int t = 0; t < kPer; ++t) rank[t] = 0;
+  for (int half = 0; half < 2; ++half) {
+    const int j0 = half * kMaxTopk, j1 = j0 + (half ? kb : ka);
+    for (int j = j0; j < j1; ++j) {
+      const float s2 = ms[w][j];
+      const int i2 = mi[w][j];
+      if (i2 < 0) continue;                // wave-uniform
+#pragma unroll
+      for (int t = 0; t < kPer; ++t)
+        rank[t] += better(s2, i2, sv[t], id[t]) || (s2 == sv[t] && i2 == id[t] && j < lane + 64 * t) ? 1 : 0;
+    }
+  }
+  int V = 0;
+#pragma unroll
+  for (int t = 0; t < kPer; ++t) {
+    V += __popcll(__ballot(id[t] >= 0));
+    if (id[t] >= 0 && rank[t] < topk) {
+      out_s[(size_t)user * topk + rank[t]] = sv[t];
+      out_i[(size_t)user * topk + rank[t]] = id[t];
+    }
+  }
+  for (int i = min(V, topk) + lane; i < topk; i += 64) {
+    out_s[(size_t)user * topk + i] = -INFINITY;
+    out_i[(size_t)user * topk + i] = -1;
+  }
+}
+
+// every list empty: (-inf, -1) (the subset form with an empty id list)
+__global__ __launch_bounds__(256) void rk_fill_empty(float* __restrict__ top_s, int32_t* __restrict__ top_i, size_t n) {
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
+    top_s[i] = -INFINITY;
+    top_i[i] = -1;
+  }
+}
+
 // ================================================================================================
 // host side
 // ================================================================================================
@@ -965,19 +1118,19 @@ bool rk_split(const RkParams& prm) {
   return num_cus() == 256;
 }
 
-template <class T, int NKT, int S, int GEO, bool FLT>
+template <class T, int NKT, int S, int GEO, bool FLT, bool SUB = false>
 int rk_launch_geo(void* stream, const RkParams& prm, bool split) {
   // d = 768 in 16-bit (config 5): the chunk count compile-time
-  void (*kern)(RkParams) = split ? rk_fused<T, NKT, S, 0, kSplit, GEO, 0, FLT> : rk_fused<T, NKT, S, 0, 1, GEO, 0, FLT>;
+  void (*kern)(RkParams) = split ? rk_fused<T, NKT, S, 0, kSplit, GEO, 0, FLT, SUB> : rk_fused<T, NKT, S, 0, 1, GEO, 0, FLT, SUB>;
   if constexpr (sizeof(T) == 2) {
     // config 5's d = 768 and K = 64 compile-time (the masked interest loops of the epilogue compile
     // away; the top-k equals the oracle's at the 16-bit bar, tests/test_gpu_corpus.py)
     constexpr int kN768 = 768 * 2 / kRB<GEO>;
     if (prm.d == 768) {
       if (NKT == 2 && prm.K == 64)
-        kern = split ? rk_fused<T, NKT, S, kN768, kSplit, GEO, 64, FLT> : rk_fused<T, NKT, S, kN768, 1, GEO, 64, FLT>;
+        kern = split ? rk_fused<T, NKT, S, kN768, kSplit, GEO, 64, FLT, SUB> : rk_fused<T, NKT, S, kN768, 1, GEO, 64, FLT, SUB>;
       else
-        kern = split ? rk_fused<T, NKT, S, kN768, kSplit, GEO, 0, FLT> : rk_fused<T, NKT, S, kN768, 1, GEO, 0, FLT>;
+        kern = split ? rk_fused<T, NKT, S, kN768, kSplit, GEO, 0, FLT, SUB> : rk_fused<T, NKT, S, kN768, 1, GEO, 0, FLT, SUB>;
     }
   }
   constexpr int NR = S == MINER_SCORE_WEIGHTED ? 2 * NKT : NKT;
@@ -1002,6 +1155,9 @@ template <class T, int NKT, int S>
 int rk_launch(void* stream, const RkParams& prm) {
   const bool split = rk_split(prm);
   const bool flt = prm.ok != nullptr || prm.E > 0;     // the filtered instantiation only when asked for
+  // the subset form: one instantiation per shape, the filtered one (either filter may be null),
+  // with the chunk count and K chosen as for the table forms
+  if (prm.ids != nullptr) return rk_launch_geo<T, NKT, S, 0, true, true>(stream, prm, split);
   // (GEO 1 — 64-byte rows through a 4-stage ring, three chunks in flight instead of one — measured
   // slower: 95.9 vs 89.7 ms per config-5 step, twice the barriers for no gain in the gather rate;
   // diagnostic builds with -DMINER_RK_GEO1 launch it)
@@ -1031,6 +1187,50 @@ int check_dims(int dtype, int d, int Dc, int K) {
   if (K > kMaxK || Dc > 32 * kDcT || d > kMaxD) return MINER_ESHAPE;
   if (d % (dtype == MINER_DTYPE_F32 ? 32 : 64)) return MINER_ESHAPE;
   return MINER_OK;
+}
+
+// miner_rank_topk_filtered and miner_rank_topk_subset (subset: the id list's checks follow the
+// table forms' checks, which keep their order and codes)
+int rk_run(void* stream, int dtype, int score_type, const void* user_mui, const void* user_proj, const void* news, int U,
+           int N, int d, int K, int topk, const int32_t* exclude_ids, int E, const uint32_t* news_ok, bool subset,
+           const int32_t* news_ids, int M, float* top_scores, int32_t* top_ids, void* workspace, size_t workspace_bytes) {
+  const int ck = check_dims(dtype, d, 1, K);
+  if (ck != MINER_OK) return ck;
+  if (score_type < MINER_SCORE_WEIGHTED || score_type > MINER_SCORE_MEAN) return MINER_EINVAL;
+  if (U < 0 || N <= 0 || topk <= 0) return MINER_EINVAL;
+  if (topk > kMaxTopk) return MINER_ESHAPE;
+  if (!user_mui || !news || !top_scores || !top_ids) return MINER_EINVAL;
+  if (score_type == MINER_SCORE_WEIGHTED && !user_proj) return MINER_EINVAL;
+  if (!aligned16(user_mui) || !aligned16(user_proj) || !aligned16(news)) return MINER_EALIGN;
+  if (E < 0 || (E > 0 && !exclude_ids)) return MINER_EINVAL;
+  if (E > kMaxL) return MINER_ESHAPE;
+  if (!aligned4(exclude_ids) || !aligned4(news_ok)) return MINER_EALIGN;
+  if (subset) {
+    if (M < 0 || (M > 0 && !news_ids)) return MINER_EINVAL;
+    if (!aligned4(news_ids)) return MINER_EALIGN;
+  }
+  if (U == 0) return MINER_OK;
+  RkParams prm{};
+  if (!aligned16(workspace)) return MINER_EALIGN;
+  if (subset && M == 0) {                  // nothing to rank: every list empty, no ranker launch
+    const size_t n = (size_t)U * topk;
+    hipLaunchKernelGGL(rk_fill_empty, dim3((unsigned)((n + 255) / 256 < 1024 ? (n + 255) / 256 : 1024)), dim3(256), 0,
+                       static_cast<hipStream_t>(stream), top_scores, top_ids, n);
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? MINER_OK : (int)e;
+  }
+  prm.mui = user_mui; prm.proj = user_proj; prm.news = news; prm.top_s = top_scores; prm.top_i = top_ids;
+  if (workspace) {
+    prm.ws_bytes = workspace_bytes;
+    prm.ws_s = static_cast<float*>(workspace);
+    prm.ws_i = reinterpret_cast<int32_t*>(static_cast<char*>(workspace) + (size_t)U * kSplit * topk * 4);
+  }
+  prm.U = U; prm.N = N; prm.d = d; prm.K = K; prm.topk = topk; prm.score_type = score_type;
+  prm.excl = E > 0 ? exclude_ids : nullptr; prm.E = E; prm.ok = news_ok;
+  prm.ids = subset ? news_ids : nullptr; prm.M = subset ? M : 0;
+  if (dtype == MINER_DTYPE_BF16) return rk_dispatch<__bf16>(stream, prm);
+  if (dtype == MINER_DTYPE_F16) return rk_dispatch<_Float16>(stream, prm);
+  return rk_dispatch<float>(stream, prm);
 }
 
 }  // namespace
@@ -1112,31 +1312,34 @@ int miner_rank_topk_filtered(void* stream, int dtype, int score_type, const void
                              const void* news, int U, int N, int d, int K, int topk, const int32_t* exclude_ids, int E,
                              const uint32_t* news_ok, float* top_scores, int32_t* top_ids, void* workspace,
                              size_t workspace_bytes) {
-  const int ck = check_dims(dtype, d, 1, K);
-  if (ck != MINER_OK) return ck;
-  if (score_type < MINER_SCORE_WEIGHTED || score_type > MINER_SCORE_MEAN) return MINER_EINVAL;
-  if (U < 0 || N <= 0 || topk <= 0) return MINER_EINVAL;
-  if (topk > kMaxTopk) return MINER_ESHAPE;
-  if (!user_mui || !news || !top_scores || !top_ids) return MINER_EINVAL;
-  if (score_type == MINER_SCORE_WEIGHTED && !user_proj) return MINER_EINVAL;
-  if (!aligned16(user_mui) || !aligned16(user_proj) || !aligned16(news)) return MINER_EALIGN;
-  if (E < 0 || (E > 0 && !exclude_ids)) return MINER_EINVAL;
-  if (E > kMaxL) return MINER_ESHAPE;
-  if (!aligned4(exclude_ids) || !aligned4(news_ok)) return MINER_EALIGN;
+  return rk_run(stream, dtype, score_type, user_mui, user_proj, news, U, N, d, K, topk, exclude_ids, E, news_ok, false,
+                nullptr, 0, top_scores, top_ids, workspace, workspace_bytes);
+}
+
+int miner_rank_topk_subset(void* stream, int dtype, int score_type, const void* user_mui, const void* user_proj,
+                           const void* news, int U, int N, int d, int K, int topk, const int32_t* exclude_ids, int E,
+                           const uint32_t* news_ok, const int32_t* news_ids, int M, float* top_scores, int32_t* top_ids,
+                           void* workspace, size_t workspace_bytes) {
+  return rk_run(stream, dtype, score_type, user_mui, user_proj, news, U, N, d, K, topk, exclude_ids, E, news_ok, true,
+                news_ids, M, top_scores, top_ids, workspace, workspace_bytes);
+}
+
+int miner_topk_merge(void* stream, const float* a_scores, const int32_t* a_ids, int ka, const float* b_scores,
+                     const int32_t* b_ids, int kb, int U, int topk, const uint32_t* news_ok, int N, float* out_scores,
+                     int32_t* out_ids) {
+  if (U < 0 || ka < 0 || kb < 0 || topk <= 0) return MINER_EINVAL;
+  if (ka > kMaxTopk || kb > kMaxTopk || topk > kMaxTopk) return MINER_ESHAPE;
+  if ((ka > 0 && (!a_scores || !a_ids)) || (kb > 0 && (!b_scores || !b_ids)) || !out_scores || !out_ids) return MINER_EINVAL;
+  if (news_ok && N <= 0) return MINER_EINVAL;
+  if (!aligned4(a_scores) || !aligned4(a_ids) || !aligned4(b_scores) || !aligned4(b_ids) || !aligned4(news_ok) ||
+      !aligned4(out_scores) || !aligned4(out_ids))
+    return MINER_EALIGN;
   if (U == 0) return MINER_OK;
-  RkParams prm{};
-  if (!aligned16(workspace)) return MINER_EALIGN;
-  prm.mui = user_mui; prm.proj = user_proj; prm.news = news; prm.top_s = top_scores; prm.top_i = top_ids;
-  if (workspace) {
-    prm.ws_bytes = workspace_bytes;
-    prm.ws_s = static_cast<float*>(workspace);
-    prm.ws_i = reinterpret_cast<int32_t*>(static_cast<char*>(workspace) + (size_t)U * kSplit * topk * 4);
-  }
-  prm.U = U; prm.N = N; prm.d = d; prm.K = K; prm.topk = topk; prm.score_type = score_type;
-  prm.excl = E > 0 ? exclude_ids : nullptr; prm.E = E; prm.ok = news_ok;
-  if (dtype == MINER_DTYPE_BF16) return rk_dispatch<__bf16>(stream, prm);
-  if (dtype == MINER_DTYPE_F16) return rk_dispatch<_Float16>(stream, prm);
-  return rk_dispatch<float>(stream, prm);
+  hipLaunchKernelGGL(topk_merge, dim3((U + kMergeUsers - 1) / kMergeUsers), dim3(64 * kMergeUsers), 0,
+                     static_cast<hipStream_t>(stream), a_scores, a_ids, ka, b_scores, b_ids, kb, U, topk, news_ok, N,
+                     out_scores, out_ids);
+  const hipError_t e = hipGetLastError();
+  return e == hipSuccess ? MINER_OK : (int)e;
 }
 
 }  // extern "C"

@@ -1,0 +1,119 @@
+"""miner_rank_topk_subset and miner_topk_merge on the host: both symbols are exported, every
+argument error the header documents (include/miner_corpus.h) is answered with its code before any
+launch — with U = 0 or M = 0 where the arguments are accepted, so nothing launches —, the checks of
+miner_rank_topk_filtered still come first, and the ABI number is unchanged. The AddressSanitizer
+driver of the two entry points (tests/native/abi_errors_subset.cpp) runs as tests/test_asan_abi.py
+runs the first one. No compute call is made (runs on CPU-only machines)."""
+import ctypes
+import os
+import subprocess
+
+import pytest
+
+from miner_amd import _lib, build, corpus
+
+OK, EINVAL, ESHAPE, EALIGN = 0, -1, -2, -3
+F32, WEIGHTED = _lib.DTYPE_F32, _lib.SCORE_WEIGHTED
+P = ctypes.c_void_p
+
+
+@pytest.fixture(scope="module")
+def lib():
+    if not os.path.exists(_lib.LIB_PATH):
+        build.build_library()
+    return _lib.lib()
+
+
+def subset(lib, *, excl=16, E=4, ok=16, ids=16, M=8, U=0, topk=10, K=32, d=64, ws=None, mui=16):
+    p = lambda v: None if v is None else P(v)
+    return lib.miner_rank_topk_subset(None, F32, WEIGHTED, p(mui), P(16), P(16), U, 100, d, K, topk, p(excl), E, p(ok),
+                                      p(ids), M, P(16), P(16), p(ws), 0)
+
+
+def merge(lib, *, a_s=16, a_i=32, ka=10, b_s=48, b_i=64, kb=10, U=0, topk=10, ok=None, N=0, o_s=80, o_i=96):
+    p = lambda v: None if v is None else P(v)
+    return lib.miner_topk_merge(None, p(a_s), p(a_i), ka, p(b_s), p(b_i), kb, U, topk, p(ok), N, p(o_s), p(o_i))
+
+
+def test_symbols_are_exported(lib):
+    raw = ctypes.CDLL(_lib.LIB_PATH)
+    for name in ("miner_rank_topk_subset", "miner_topk_merge"):
+        assert name in _lib.SIGNATURES
+        assert ctypes.cast(getattr(raw, name), ctypes.c_void_p).value
+    assert lib.miner_abi_version() == 6 == _lib.ABI_VERSION      # the entry points are additive
+
+
+def test_subset_argument_errors_before_any_launch(lib):
+    assert subset(lib, M=-1) == EINVAL
+    assert subset(lib, ids=None, M=3) == EINVAL                  # a length without a list
+    assert subset(lib, ids=18) == EALIGN                          # 4-byte alignment
+    assert subset(lib, ids=18, M=0) == EALIGN
+    assert subset(lib, U=3, M=-1) == EINVAL                       # the same with users: still no launch
+    assert subset(lib, U=3, ids=None, M=3) == EINVAL
+    assert subset(lib, U=3, ids=18) == EALIGN
+    assert subset(lib, U=3, ids=16, M=0, ws=8) == EALIGN          # the workspace check, before the M == 0 return
+    # accepted argument sets: U = 0 returns after validation
+    assert subset(lib) == OK
+    assert subset(lib, ids=None, M=0) == OK
+    assert subset(lib, ids=20, M=0) == OK
+    assert subset(lib, excl=None, E=0, ok=None) == OK             # both filters may be NULL
+
+
+def test_the_filtered_checks_still_come_first(lib):
+    # each with an invalid id list as well: the older check's code is the one returned
+    bad = dict(ids=None, M=-5)
+    assert subset(lib, topk=0, **bad) == EINVAL
+    assert subset(lib, topk=corpus.MAX_TOPK + 1, **bad) == ESHAPE
+    assert subset(lib, K=65, **bad) == ESHAPE
+    assert subset(lib, d=100, **bad) == ESHAPE
+    assert subset(lib, mui=20, **bad) == EALIGN
+    assert subset(lib, E=corpus.MAX_L + 1, **bad) == ESHAPE
+    assert subset(lib, excl=18, ids=None, M=3) == EALIGN          # a misaligned filter before the NULL list
+    assert subset(lib, ok=17, ids=None, M=3) == EALIGN
+    assert subset(lib, E=-1, ids=18) == EINVAL                    # E < 0 before the misaligned list
+    assert subset(lib, mui=None) == EINVAL
+
+
+def test_merge_argument_errors_before_any_launch(lib):
+    assert merge(lib, U=-1) == EINVAL
+    assert merge(lib, ka=-1) == EINVAL
+    assert merge(lib, kb=-1) == EINVAL
+    assert merge(lib, topk=0) == EINVAL
+    assert merge(lib, ka=corpus.MAX_TOPK + 1) == ESHAPE
+    assert merge(lib, kb=corpus.MAX_TOPK + 1) == ESHAPE
+    assert merge(lib, topk=corpus.MAX_TOPK + 1) == ESHAPE
+    assert merge(lib, a_s=None) == EINVAL
+    assert merge(lib, a_i=None) == EINVAL
+    assert merge(lib, b_s=None) == EINVAL
+    assert merge(lib, b_i=None) == EINVAL
+    assert merge(lib, o_s=None) == EINVAL
+    assert merge(lib, o_i=None) == EINVAL
+    assert merge(lib, ok=16, N=0) == EINVAL                       # a bitmap needs its size
+    for name in ("a_s", "a_i", "b_s", "b_i", "o_s", "o_i"):
+        assert merge(lib, **{name: 18}) == EALIGN, name
+    assert merge(lib, ok=18, N=100) == EALIGN
+    assert merge(lib, U=3, ka=300) == ESHAPE                      # with users: still before any launch
+    assert merge(lib, U=3, b_i=18) == EALIGN
+    # accepted: U = 0 returns after validation; an empty list needs no pointers
+    assert merge(lib) == OK
+    assert merge(lib, ka=corpus.MAX_TOPK, kb=corpus.MAX_TOPK, topk=corpus.MAX_TOPK) == OK
+    assert merge(lib, a_s=None, a_i=None, ka=0) == OK
+    assert merge(lib, b_s=None, b_i=None, kb=0) == OK
+    assert merge(lib, ok=16, N=100) == OK
+
+
+@pytest.fixture(scope="module")
+def driver():
+    try:
+        return build.build_asan_driver_subset()
+    except RuntimeError as e:                       # no ROCm toolchain in this environment
+        pytest.skip(f"asan build unavailable: {e}")
+
+
+def test_new_entry_points_under_asan(driver):
+    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=0:abort_on_error=0:halt_on_error=1")
+    res = subprocess.run([driver], capture_output=True, text=True, timeout=300, env=env)
+    out = res.stdout + res.stderr
+    assert "AddressSanitizer" not in out, out[-4000:]
+    assert res.returncode == 0, out[-4000:]
+    assert "0 failures" in res.stdout, out[-2000:]
