@@ -19,6 +19,9 @@
  *   miner_rank_topk_subset(...)    the same over the table rows of an id list only (cost by the
  *                             list's length), and miner_topk_merge(...) to fold its lists into
  *                             lists ranked earlier: incremental ranking of a changing corpus.
+ *   miner_score_pairs(...)    the click score of given (user, news) pairs, with the ranker's bits, and
+ *   miner_rank_count(...)     per user and target (score, id), how many news rank before it: exact
+ *                             full-corpus ranks, still without the U x N matrix.
  *
  * Conventions are those of miner_score.h. dtype: MINER_DTYPE_F32 (exact fp32, parity mode),
  * MINER_DTYPE_BF16 or MINER_DTYPE_F16 (16-bit operands, fp32 accumulation and softmax).
@@ -146,6 +149,49 @@ int miner_rank_topk_subset(void* stream, int dtype, int score_type, const void* 
 int miner_topk_merge(void* stream, const float* a_scores, const int32_t* a_ids, int ka, const float* b_scores,
                      const int32_t* b_ids, int kb, int U, int topk, const uint32_t* news_ok, int N,
                      float* out_scores, int32_t* out_ids);
+
+/*
+ * The click score of chosen (user, news) pairs from cached user vectors: the second stage of a
+ * recommender (re-score a short candidate list per user), and the refresh of a served list.
+ *   scores[u, c] = click score of (user u, news[cand_ids[u, c]]), bit for bit the score the ranking
+ *   forms compute for that pair (every dtype, score type, K, d: the same d-chunk sequence, in-lane K
+ *   reductions and lane-half exchanges, with the chunk count and K compile-time where the ranking
+ *   forms have them).
+ *   cand_ids    [U, C] int32 device pointer, 4-byte aligned, C >= 0, any order, repeats allowed; an
+ *               id outside [0, N) gives -inf and no row is read for it.
+ *   scores      [U, C] fp32 out, 4-byte aligned.
+ * Only the U x C rows are fetched and multiplied (a workgroup takes one user and 256 entries of its
+ * list per step). After the checks shared with miner_rank_topk_filtered (dtype, d, K, score_type,
+ * U, N, the user and table pointers and their alignment), in its order and with its codes: C < 0,
+ * or C > 0 with a NULL cand_ids or scores: MINER_EINVAL; a misaligned cand_ids or scores:
+ * MINER_EALIGN (all before any launch). U == 0 or C == 0: MINER_OK with no launch.
+ */
+int miner_score_pairs(void* stream, int dtype, int score_type, const void* user_mui, const void* user_proj,
+                      const void* news, int U, int N, int d, int K, const int32_t* cand_ids, int C, float* scores);
+
+#define MINER_CORPUS_MAX_TARGETS 64
+
+/*
+ * The counting form of the ranker: exact full-corpus ranks without a list.
+ *   counts[u, j] = #{ n in [0, N) : news_ok(n) and (score(u, n), n) ranks before
+ *                    (target_scores[u, j], target_ids[u, j]) in the ranker's total order
+ *                    (score desc, id asc) }.
+ *   target_scores [U, T] fp32, target_ids [U, T] int32, 1 <= T <= MINER_CORPUS_MAX_TARGETS;
+ *   news_ok     as in miner_rank_topk_filtered (NULL: every news); counts [U, T] int32 out.
+ * With target_scores from miner_score_pairs on target_ids, counts[u, j] is the 0-based rank of the
+ * target among the eligible news: the stream's score of the target's own row equals the given one
+ * bit for bit, so the target does not count itself, and ties rank by id. A news whose score is NaN
+ * is never counted; a NaN target score counts nothing. The table is streamed once for all T
+ * targets; there is no per-user exclusion list (subtract the excluded ids that rank before the
+ * target, scored with miner_score_pairs — corpus.rank_of does). One launch, the unsplit form: no
+ * workspace, no atomics, a deterministic result.
+ * All pointers are device pointers, 4-byte aligned. After the shared checks (above): T <= 0, or a
+ * NULL target_scores / target_ids / counts: MINER_EINVAL; T > MINER_CORPUS_MAX_TARGETS:
+ * MINER_ESHAPE; a misaligned pointer: MINER_EALIGN (all before any launch). U == 0: MINER_OK.
+ */
+int miner_rank_count(void* stream, int dtype, int score_type, const void* user_mui, const void* user_proj,
+                     const void* news, int U, int N, int d, int K, const float* target_scores,
+                     const int32_t* target_ids, int T, const uint32_t* news_ok, int32_t* counts);
 
 #ifdef __cplusplus
 }

@@ -119,6 +119,7 @@ def build_library(force: bool = False, verbose: bool = False, debug: bool = Fals
 
 ASAN_DRIVER = os.path.join(ROOT, "tests", "native", "abi_errors.cpp")
 ASAN_DRIVER_SUBSET = os.path.join(ROOT, "tests", "native", "abi_errors_subset.cpp")
+ASAN_DRIVER_RANK = os.path.join(ROOT, "tests", "native", "abi_errors_rank.cpp")
 
 
 def build_asan_driver(force: bool = False, verbose: bool = False, driver: str = ASAN_DRIVER) -> str:
@@ -170,9 +171,16 @@ def build_asan_driver_subset(force: bool = False, verbose: bool = False) -> str:
     return build_asan_driver(force=force, verbose=verbose, driver=ASAN_DRIVER_SUBSET)
 
 
+def build_asan_driver_rank(force: bool = False, verbose: bool = False) -> str:
+    """build/asan/abi_errors_rank: the error paths of miner_score_pairs and miner_rank_count
+    (tests/native/abi_errors_rank.cpp; run by tests/test_corpus_rank_host.py)."""
+    return build_asan_driver(force=force, verbose=verbose, driver=ASAN_DRIVER_RANK)
+
+
 if __name__ == "__main__":
     if "--asan" in sys.argv:
         print(build_asan_driver(force="--force" in sys.argv, verbose=True))
         print(build_asan_driver_subset(verbose=True))
+        print(build_asan_driver_rank(verbose=True))
     else:
         print(build_library(force="--force" in sys.argv, verbose=True, debug="--debug" in sys.argv))

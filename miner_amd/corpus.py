@@ -7,6 +7,11 @@ d=768, fp16), backed by libminer_hip.so (include/miner_corpus.h).
     rank_topk(..., exclude_ids=clicked, eligible=fresh)    # per-user "not these", table-wide "only these"
     rank_topk(..., news_ids=new_rows)                      # only these rows are read: cost by their count
     lists = update_topk(lists, mui, proj, news_table, new_rows)   # ... and folded into served lists
+    scores = score_pairs(mui, proj, news_table, cand_ids)  # [U, C] chosen pairs, the ranker's own bits
+    ranks, scores = rank_of(mui, proj, news_table, clicked, exclude_ids=history)   # exact ranks among all N
+    per_user, means = corpus_metrics(ranks, n_ranked)      # recall@k / hit@k / ndcg@k / mrr / auc
+    ranks, metrics = evaluate_corpus(news_table, his_ids, his_mask, packed, clicked)  # the full-ranking protocol
+    lists = rescore_topk(lists, new_mui, new_proj, news_table)    # served lists after the users changed
 
 The click score of (user, news) is the reference's (src/model/model.py:127-134, 213-214) with the
 impression's candidate set replaced by the whole news table; ties rank the lower news id first.
@@ -305,6 +310,239 @@ def update_topk(lists, user_mui: Tensor, user_proj: Optional[Tensor], news: Tens
     fresh = rank_topk(user_mui, user_proj, news, k, score_type=score_type, exclude_ids=exclude_ids, eligible=ok,
                       news_ids=news_ids)
     return merge_topk(old, fresh, k, eligible=ok)
+
+
+MAX_TARGETS = 64
+
+
+def _rank_operands(user_mui: Tensor, user_proj: Optional[Tensor], news: Tensor, score_type: str):
+    """The checks and conversions rank_topk makes of the user vectors and the table."""
+    st = _lib.SCORE_TYPES.get(score_type)
+    if st is None or st == _lib.SCORE_NONE:
+        raise ValueError("Invalid method of aggregating matching score")  # model.py:136
+    _require_device(user_mui, user_proj, news)
+    dtype = user_mui.dtype
+    dt = _code(dtype)
+    mui = _contig(user_mui, dtype)
+    proj = _contig(user_proj, dtype) if st == _lib.SCORE_WEIGHTED else None
+    if st == _lib.SCORE_WEIGHTED and proj is None:
+        raise ValueError("score_type 'weighted' needs user_proj")
+    tab = _contig(news, dtype)
+    if mui.dim() != 3 or tab.dim() != 2 or tab.shape[1] != mui.shape[2] or (proj is not None and proj.shape != mui.shape):
+        raise ValueError("shape mismatch between user vectors and the news table")
+    return st, dt, mui, proj, tab
+
+
+def _check_ids(ids, U: int, what: str) -> None:
+    """Shape and dtype of an id matrix (before anything touches the device)."""
+    if not isinstance(ids, Tensor) or ids.dim() != 2 or ids.shape[0] != U or ids.is_floating_point() \
+            or ids.is_complex() or ids.dtype == torch.bool:
+        raise ValueError(f"{what} must be an integer [{U}, C] tensor")
+
+
+def _id_matrix(ids: Tensor, U: int, N: int, what: str) -> Tensor:
+    """An integer [U, C] tensor of news ids -> int64, ids outside [0, N) replaced by -1."""
+    _check_ids(ids, U, what)
+    _require_device(ids)
+    ids = ids.to(torch.int64)
+    return torch.where((ids >= 0) & (ids < N), ids, -1)
+
+
+def _bits_at(words: Tensor, ids: Tensor) -> Tensor:
+    """Eligibility of the news ``ids`` (int64, any shape, -1 = none) under the packed bitmap."""
+    safe = ids.clamp(min=0)
+    return (((words[safe >> 5].to(torch.int64) >> (safe & 31)) & 1) != 0) & (ids >= 0)
+
+
+def _score_pairs(st, dt, mui, proj, tab, ids64: Tensor) -> Tensor:
+    U, K, d = mui.shape
+    C = ids64.shape[1]
+    out = torch.empty(U, C, dtype=torch.float32, device=mui.device)
+    if U == 0 or C == 0:
+        return out
+    ids = ids64.to(torch.int32).contiguous()
+    with torch.cuda.device(mui.device):
+        rc = _lib.lib().miner_score_pairs(_stream(mui.device), dt, st, _ptr(mui), _ptr(proj), _ptr(tab), U, tab.shape[0],
+                                          d, K, _ptr(ids), C, _ptr(out))
+    _lib.check(rc, "miner_score_pairs")
+    return out
+
+
+def score_pairs(user_mui: Tensor, user_proj: Optional[Tensor], news: Tensor, cand_ids: Tensor, *,
+                score_type: str = "weighted") -> Tensor:
+    """The click score of chosen pairs: scores[u, c] of (user u, news[cand_ids[u, c]]), fp32 [U, C] —
+    bit for bit what rank_topk computes for that pair, from the cached user vectors. cand_ids [U, C]
+    of any integer dtype, any order, repeats allowed; an id outside [0, N) (a -1 padding) gives -inf.
+    Only the U x C rows are read: the second stage of a recommender, or the refresh of a served list
+    (rescore_topk)."""
+    _check_ids(cand_ids, user_mui.shape[0], "cand_ids")
+    st, dt, mui, proj, tab = _rank_operands(user_mui, user_proj, news, score_type)
+    return _score_pairs(st, dt, mui, proj, tab, _id_matrix(cand_ids, mui.shape[0], tab.shape[0], "cand_ids"))
+
+
+def _better(s: Tensor, i: Tensor, s2: Tensor, i2: Tensor) -> Tensor:
+    """The ranker's total order: (s, i) before (s2, i2)."""
+    return (s > s2) | ((s == s2) & (i < i2))
+
+
+def _rank_of(user_mui, user_proj, news, target_ids, score_type, exclude_ids, eligible):
+    _check_ids(target_ids, user_mui.shape[0], "target_ids")
+    if not 1 <= target_ids.shape[1] <= MAX_TARGETS:
+        raise ValueError(f"target_ids holds {target_ids.shape[1]} targets per user, outside [1, {MAX_TARGETS}]")
+    if exclude_ids is not None:
+        _check_ids(exclude_ids, user_mui.shape[0], "exclude_ids")
+        if exclude_ids.shape[1] > MAX_L:
+            raise ValueError(f"exclude_ids holds {exclude_ids.shape[1]} ids per user, more than {MAX_L}")
+    st, dt, mui, proj, tab = _rank_operands(user_mui, user_proj, news, score_type)
+    U, K, d = mui.shape
+    N = tab.shape[0]
+    dev = mui.device
+    tid = _id_matrix(target_ids, U, N, "target_ids")
+    T = tid.shape[1]
+    _require_device(exclude_ids, eligible)
+    ex = None
+    if exclude_ids is not None:
+        ex = _id_matrix(exclude_ids, U, N, "exclude_ids")
+        if ex.shape[1] == 0:
+            ex = None
+    ok = None if eligible is None else _eligible_words(eligible, N)
+    tgt_s = _score_pairs(st, dt, mui, proj, tab, tid)
+    counts = torch.empty(U, T, dtype=torch.int32, device=dev)
+    if U:
+        tid32 = tid.to(torch.int32).contiguous()
+        with torch.cuda.device(dev):
+            rc = _lib.lib().miner_rank_count(_stream(dev), dt, st, _ptr(mui), _ptr(proj), _ptr(tab), U, N, d, K,
+                                             _ptr(tgt_s), _ptr(tid32), T, _ptr(ok), _ptr(counts))
+        _lib.check(rc, "miner_rank_count")
+    appears = (tid >= 0) & ~torch.isnan(tgt_s)
+    if ok is not None:
+        appears &= _bits_at(ok, tid)
+    n_ok = N if ok is None else int(_bits_at(ok, torch.arange(N, device=dev)).sum())
+    survivors = torch.full((U,), n_ok, dtype=torch.int64, device=dev)
+    ranks = counts.to(torch.int64)
+    if ex is not None and U:
+        # the excluded news the kernel counted: distinct, in range, eligible, ranking before the target
+        # — their scores are the stream's own bits (score_pairs), so the correction is exact
+        ex = torch.sort(ex, dim=1).values
+        ex[:, 1:] = torch.where(ex[:, 1:] == ex[:, :-1], -1, ex[:, 1:])
+        ex_s = _score_pairs(st, dt, mui, proj, tab, ex)
+        live = ex >= 0 if ok is None else _bits_at(ok, ex)
+        survivors -= live.sum(dim=1)
+        E = ex.shape[1]
+        step = max(1, (1 << 26) // max(1, E * T))             # users per [u, E, T] comparison block
+        for u0 in range(0, U, step):
+            sl = slice(u0, u0 + step)
+            before = live[sl, :, None] & _better(ex_s[sl, :, None], ex[sl, :, None], tgt_s[sl, None, :], tid[sl, None, :])
+            ranks[sl] -= before.sum(dim=1)
+            appears[sl] &= ~(ex[sl, :, None] == tid[sl, None, :]).any(dim=1)
+    ranks = torch.where(appears, ranks, -1).to(torch.int32)
+    return ranks, tgt_s, survivors
+
+
+def rank_of(user_mui: Tensor, user_proj: Optional[Tensor], news: Tensor, target_ids: Tensor, *,
+            score_type: str = "weighted", exclude_ids: Optional[Tensor] = None, eligible: Optional[Tensor] = None):
+    """Exact full-corpus ranks: (ranks int32 [U, T], scores fp32 [U, T]) for target_ids [U, T]
+    (integer, T <= 64). ranks[u, j] is the 0-based position news target_ids[u, j] holds in user u's
+    complete filtered list — what rank_topk with the same ``exclude_ids`` / ``eligible`` would return
+    if topk were N — and -1 if it would not appear (id outside [0, N), not eligible, in
+    exclude_ids[u], or a NaN score). The table is streamed once for all T targets and no list is
+    kept (miner_rank_count); the targets' scores come from score_pairs, whose bits are the stream's
+    own, so the count is exact and a tie ranks by id. The exclusion list is a correction on the device:
+    its distinct, in-range, eligible ids that rank before the target are subtracted."""
+    ranks, scores, _ = _rank_of(user_mui, user_proj, news, target_ids, score_type, exclude_ids, eligible)
+    return ranks, scores
+
+
+def corpus_metrics(ranks: Tensor, n_ranked: Optional[Tensor] = None, *, ks=(5, 10)):
+    """Full-ranking metrics of ranks [U, T] (0-based rank of each held-out click in the user's list
+    over the corpus; -1: no target in that slot). Pure torch, any device. Returns (per_user, means):
+    per_user[name] a float64 [U] tensor (NaN for a user with no target), means[name] its mean over
+    the users that have at least one target.
+      recall@k  share of the user's targets ranked below k;  hit@k  1 if any is
+      mrr       mean over the targets of 1 / (rank + 1)  (the reference's compute_mrr_score)
+      ndcg@k    binary gains, discount log2(rank + 2), ideal DCG over min(#targets, k) positions
+      auc       (with n_ranked [U], the number of news in each user's list) the share of (target,
+                non-target) pairs the strict total order puts the right way round; NaN where every
+                ranked news is a target."""
+    if ranks.dim() != 2 or ranks.is_floating_point():
+        raise ValueError("ranks must be an integer [U, T] tensor")
+    r = ranks.to(torch.int64)
+    has = r >= 0
+    m = has.sum(dim=1).to(torch.float64)
+    some = m > 0
+    nan = torch.full_like(m, float("nan"))
+    rf = r.clamp(min=0).to(torch.float64)
+    per = {}
+    for k in ks:
+        below = has & (r < k)
+        per[f"recall@{k}"] = torch.where(some, below.sum(dim=1) / m, nan)
+        per[f"hit@{k}"] = torch.where(some, below.any(dim=1).to(torch.float64), nan)
+        dcg = torch.where(below, 1.0 / torch.log2(rf + 2.0), 0.0).sum(dim=1)
+        pos = torch.arange(min(k, r.shape[1]), device=r.device, dtype=torch.float64)
+        ideal = torch.where(pos[None, :] < m[:, None], 1.0 / torch.log2(pos + 2.0)[None, :], 0.0).sum(dim=1)
+        per[f"ndcg@{k}"] = torch.where(some, dcg / ideal, nan)
+    per["mrr"] = torch.where(some, torch.where(has, 1.0 / (rf + 1.0), 0.0).sum(dim=1) / m, nan)
+    if n_ranked is not None:
+        n = n_ranked.to(r.device, torch.float64)
+        # target i (in rank order) has n - 1 - rank_i news behind it, m - 1 - i of them targets
+        good = torch.where(has, n[:, None] - 1.0 - rf, 0.0).sum(dim=1) - m * (m - 1.0) / 2.0
+        per["auc"] = torch.where(some & (n > m), good / (m * (n - m)), nan)
+    means = {}
+    for name, v in per.items():
+        v = v[some & ~torch.isnan(v)]
+        means[name] = float(v.mean()) if v.numel() else float("nan")
+    return per, means
+
+
+def rescore_topk(lists, user_mui: Tensor, user_proj: Optional[Tensor], news: Tensor, *,
+                 score_type: str = "weighted", eligible: Optional[Tensor] = None):
+    """Served lists (scores [U,k], ids [U,k]) after the users' vectors changed: the lists' ids are
+    scored again with score_pairs and re-sorted (and, with ``eligible``, pruned) by merge_topk. Returns
+    lists of the same width — for each user, rank_topk(news_ids=<its old ids>) bit for bit."""
+    _, ids = _list_pair(lists, "lists")
+    if ids.shape[1] < 1:
+        raise ValueError("lists must hold at least one entry per user")
+    fresh = score_pairs(user_mui, user_proj, news, ids, score_type=score_type)
+    empty = (fresh[:, :0], ids[:, :0])
+    return merge_topk(empty, (fresh, ids), ids.shape[1], eligible=eligible)
+
+
+def evaluate_corpus(news: Tensor, his_ids: Tensor, his_mask: Tensor, packed: EncoderWeights, target_ids: Tensor, *,
+                    ks=(5, 10), batch: int = 16384, exclude_history: bool = True,
+                    exclude_ids: Optional[Tensor] = None, eligible: Optional[Tensor] = None,
+                    his_bias: Optional[Tensor] = None, score_type: str = "weighted"):
+    """The full-ranking evaluation protocol on one GPU's share of the users: rank_corpus's loop with
+    rank_of in place of rank_topk. Every user is encoded from its history and each held-out click
+    target_ids[u, j] (-1: no target in that slot) is ranked among all N news, the user's history
+    (``exclude_history``) and ``exclude_ids`` left out, ``eligible`` as in rank_topk. Returns
+    (ranks int32 [U, T], metrics): corpus_metrics' means — recall@k, hit@k, ndcg@k, mrr, auc. Each
+    user's ranks are independent of the batching."""
+    if batch <= 0:
+        raise ValueError("batch must be positive")
+    U = his_ids.shape[0]
+    dev = news.device
+    _require_device(news, his_ids, his_mask, target_ids, exclude_ids, eligible)
+    excl = exclude_ids
+    if excl is not None and (excl.dim() != 2 or excl.shape[0] != U):
+        raise ValueError(f"exclude_ids must be [{U}, E]")
+    if exclude_history:
+        seen = torch.where(his_mask.to(torch.bool), his_ids, -1).to(torch.int32)   # padded slots exclude nothing
+        excl = seen if excl is None else torch.cat([seen, excl.to(torch.int32)], dim=1)
+    if excl is not None and excl.shape[1] > MAX_L:
+        raise ValueError(f"{excl.shape[1]} excluded ids per user, more than {MAX_L}")
+    if target_ids.dim() != 2 or target_ids.shape[0] != U:
+        raise ValueError(f"target_ids must be [{U}, T]")
+    ok = None if eligible is None else _eligible_words(eligible, news.shape[0])   # packed once
+    ranks = torch.empty(U, target_ids.shape[1], dtype=torch.int32, device=dev)
+    survivors = torch.empty(U, dtype=torch.int64, device=dev)
+    with_proj = score_type == "weighted"
+    for u0 in range(0, U, batch):
+        u1 = min(U, u0 + batch)
+        mui, proj = encode_users(news, his_mask[u0:u1], packed, his_ids=his_ids[u0:u1],
+                                 his_bias=None if his_bias is None else his_bias[u0:u1], with_proj=with_proj)
+        ranks[u0:u1], _, survivors[u0:u1] = _rank_of(mui, proj, news, target_ids[u0:u1], score_type,
+                                                     None if excl is None else excl[u0:u1], ok)
+    return ranks, corpus_metrics(ranks, survivors, ks=ks)[1]
 
 
 def rank_corpus(news: Tensor, his_ids: Tensor, his_mask: Tensor, packed: EncoderWeights, topk: int, *,

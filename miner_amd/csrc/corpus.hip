@@ -18,7 +18,10 @@
 //             mui) for its 64 news, so the click score (softmax over K of proj·e weighting mui·e,
 //             model.py:127-134, 213-214) is an in-register epilogue plus one lane-half exchange. Each
 //             workgroup owns whole users: a running top-k per user in LDS, threshold-filtered, so
-//             the U x N scores never leave the CU.
+//             the U x N scores never leave the CU. Two more forms of the same kernel share its
+//             contraction and score epilogue bit for bit: the counting form (per user and target,
+//             how many news rank before it: exact full-corpus ranks without a list) and the pair
+//             form (the scores of a per-user id list, U x C rows only).
 #include <hip/hip_runtime.h>
 #include <stdlib.h>
 #include <stdint.h>
@@ -451,7 +454,10 @@ struct RkParams {
   const uint32_t* ok;      // ceil(N / 32) words, bit n & 31 of word n >> 5: news n may be ranked (NULL: all)
   int U, N, d, K, topk, score_type, E;
   const int32_t* ids;      // SUB: the news rows to rank, news[ids[pos]] for pos in [0, M); distinct ids
-  int M;
+  int M;                   //      (pair form: [U][M], user u's list at ids + u·M; repeats allowed)
+  const float* tgt_s;      // counting form: [U][T] target scores and ids; the counts go to top_i [U][T]
+  const int32_t* tgt_i;
+  int T;
 };
 
 // S > 1 (S = 8, grid = 256): the news steps are dealt to S slices (step st of slice s is news step
@@ -504,8 +510,26 @@ __device__ __forceinline__ void vm_wait_n() { asm volatile("s_waitcnt vmcnt(%0)"
 template <int GEO> constexpr int kRB = GEO ? 64 : 128;
 template <int GEO> constexpr int kRing = GEO ? 4 : 2;
 
+// a wave-uniform word from global memory through the scalar cache (s_load, counted by lgkmcnt, not
+// behind the vector loads and LDS-DMAs in flight)
+__device__ __forceinline__ unsigned rk_sload(const uint32_t* q) {
+  return *(const __attribute__((address_space(4))) uint32_t*)(uintptr_t)q;
+}
+
 // total order of ranked entries: higher score first, then lower news id
 __device__ __forceinline__ bool better(float s, int i, float s2, int i2) { return s > s2 || (s == s2 && i < i2); }
+
+// The same order as one unsigned 64-bit compare, for the counting form: better(s, i, s2, i2) ==
+// (key(s, i) > key(s2, i2)) with key = rk_okey(score) << 32 | rk_ikey(id), for scores that are not
+// NaN. rk_okey: the float's bits made monotone (-0 taken as +0, as the float compare takes it;
+// integer operations only, so nothing is rounded or flushed); every real score, -inf included, has
+// a key half >= 0x007fffff. rk_ikey: a lower (signed) id gives a greater key.
+__device__ __forceinline__ unsigned rk_okey(float s) {
+  unsigned u = __float_as_uint(s);
+  if (u == 0x80000000u) u = 0u;
+  return u ^ ((unsigned)((int)u >> 31) | 0x80000000u);
+}
+__device__ __forceinline__ unsigned rk_ikey(int id) { return (unsigned)id ^ 0x7fffffffu; }
 
 template <int NR, int GEO = 0, bool FLT = false>
 struct RkLds {
@@ -526,10 +550,27 @@ struct RkLds {
 // pos is news[ids[pos]], gathered with one address per lane; a candidate's identity — in the
 // threshold test, the filters and the staged entry — is its table id ids[pos], so the list does not
 // depend on the order of the ids.
+// MODE: what the epilogue does with a score. kRank: the running top-k above. kCount (the counting
+// form, RkParams tgt_s / tgt_i / T): no list; every score of an eligible news (the bitmap, rows < N)
+// is compared with the tile's targets, [kUT][kMaxT] (score, id) pairs in LDS (as 64-bit keys in the
+// ranker's order, rk_okey / rk_ikey), and per target the scores that rank before it are counted —
+// lane j of a wave keeps its count for target j, the user's
+// four nsub waves are summed in LDS at the tile's end and counts[u][0..T) leaves in one vector store
+// (S = 1: a user belongs to one workgroup, so no atomics and a deterministic result). kPair (the
+// pair form, with SUB): a tile is ONE user, in both uu slots, against 256 entries per step of that
+// user's own id list ids[u][0..M); the score goes to top_s[u][pos], -inf for an id outside [0, N).
+// The d-chunk loop, the K reductions and the lane-half exchanges are the ones of kRank, so a pair's
+// score has the same bits in all three.
+constexpr int kRank = 0, kCount = 1, kPair = 2;
+constexpr int kMaxT = MINER_CORPUS_MAX_TARGETS;
+
 template <class T, int NKT, int SCORE, int NCH = 0, int S = 1, int GEO = 0, int KC = 0, bool FLT = false,   // KC: K compile-time (0: run time)
-          bool SUB = false>
+          bool SUB = false, int MODE = kRank>
 __global__ __launch_bounds__(kThreads) void rk_fused(RkParams p) {
   static_assert(!SUB || (FLT && GEO == 0), "the subset form: a filtered form with one chunk in flight");
+  static_assert(MODE == kRank || (S == 1 && GEO == 0 && SUB == (MODE == kPair)), "counting and pair forms: unsplit, GEO 0");
+  static_assert(kMaxT == 64 && kUT * kMaxT * 8 <= kUT * kMaxTopk * 8 && kUT * 4 * kMaxT * 4 <= 2 * kUT * kNT * 8,
+                "one target per lane; the targets in the list area, the partial counts in the staging area");
   extern __shared__ __attribute__((aligned(16))) char smem[];
   constexpr bool kW = SCORE == MINER_SCORE_WEIGHTED;
   constexpr int NR = kW ? 2 * NKT : NKT;            // row tiles per user: mui (and proj)
@@ -541,7 +582,7 @@ __global__ __launch_bounds__(kThreads) void rk_fused(RkParams p) {
   const int nchunk = NCH > 0 ? NCH : d * (int)sizeof(T) / RB;
   const int NP = SUB ? p.M : N;                                    // news positions: table rows, or list entries
   const int nsteps = ((NP + kNT - 1) / kNT + S - 1) / S;           // news steps per slice
-  const int ntiles = (p.U + kUT - 1) / kUT;
+  const int ntiles = MODE == kPair ? p.U : (p.U + kUT - 1) / kUT;   // pair form: a tile is one user
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int uu = wave >> 2, nsub = wave & 3;
   float* list_s = reinterpret_cast<float*>(smem + LD::kOffList);
@@ -550,6 +591,10 @@ __global__ __launch_bounds__(kThreads) void rk_fused(RkParams p) {
   int* stg_i = reinterpret_cast<int*>(smem + LD::kOffStage + 2 * kUT * kNT * 4);
   int* cnt = reinterpret_cast<int*>(smem + LD::kOffCnt);   // [0, kUT) list sizes, kUT + buf * kUT + uu staged
   int* excl = reinterpret_cast<int*>(smem + LD::kOffExcl);  // [kUT][kMaxL], -1 past E (FLT and p.E > 0 only)
+  // counting form (no list, nothing staged): the targets [kUT][kMaxT] and the waves' partial counts [kWaves][kMaxT]
+  [[maybe_unused]] unsigned* tg_h = reinterpret_cast<unsigned*>(smem + LD::kOffList);   // key halves: score, id
+  [[maybe_unused]] unsigned* tg_l = reinterpret_cast<unsigned*>(smem + LD::kOffList + kUT * kMaxT * 4);
+  [[maybe_unused]] int* part = reinterpret_cast<int*>(smem + LD::kOffStage);
   static_assert(kUT * kMaxL == kThreads && kMaxL == 4 * 64, "one exclusion slot per thread, four per lane of a wave");
   // the user's merging wave: 0 and 5 (two SIMDs under the wave -> SIMD w % 4 placement)
   const bool merger = wave == 5 * uu;
@@ -602,11 +647,14 @@ __global__ __launch_bounds__(kThreads) void rk_fused(RkParams p) {
     if constexpr (SUB) {
       const int lane = fresh_lane();
       const int st = S == 1 ? nsl : slice + S * nsl;
+      // pair form: the list of the user being ISSUED (tile nti; past the last tile — nothing more
+      // is issued then — the last user's, so the read stays inside the array)
+      const int32_t* ids = MODE == kPair ? p.ids + (size_t)min(nti, p.U - 1) * p.M : p.ids;
 #pragma unroll
       for (int jj = kAJ; jj < kJ; ++jj) {
         const int row = ((wave + kWaves * jj) * 64 + lane) / kUnits;
         const int pos = min(st * kNT + (row - LD::kARows), p.M - 1);
-        bid[jj] = min(max(p.ids[pos], 0), N - 1);
+        bid[jj] = min(max(ids[pos], 0), N - 1);
       }
     }
   };
@@ -624,7 +672,7 @@ __global__ __launch_bounds__(kThreads) void rk_fused(RkParams p) {
     if (jj < kAJ) {
       const int row0 = (wave + kWaves * jj) * kRpb;
       const int t = (row0 >> 5) % NR, ou = row0 / (NR * 32);
-      const int user = min(nti * kUT + ou, p.U - 1);
+      const int user = min(MODE == kPair ? nti : nti * kUT + ou, p.U - 1);
       const T* src = (kW && t >= NKT) ? proj : mui;
       rk_dma(voff[jj], reinterpret_cast<const char*>(src + (size_t)user * K * d) + nc * RB, la);
     } else if constexpr (SUB) {
@@ -737,6 +785,20 @@ __global__ __launch_bounds__(kThreads) void rk_fused(RkParams p) {
       const int eu = ti * kUT + (int)(threadIdx.x / kMaxL), es = threadIdx.x % kMaxL;
       excl[threadIdx.x] = eu < p.U && es < p.E ? p.excl[(size_t)eu * p.E + es] : -1;
     }
+    // counting form: the tile's targets as keys (rk_okey / rk_ikey), at the same point and under the
+    // same barriers. A slot past T, or of a user past U, and a target whose score is NaN hold the
+    // greatest key: nothing ranks before it.
+    int tcount = 0;            // this wave's count for target `lane` of user uu, over the tile's steps
+    if constexpr (MODE == kCount) {
+      if (threadIdx.x < kUT * kMaxT) {
+        const int eu = ti * kUT + (int)(threadIdx.x / kMaxT), es = threadIdx.x % kMaxT;
+        const bool in = eu < p.U && es < p.T;
+        const float s = in ? p.tgt_s[(size_t)eu * p.T + es] : NAN;
+        const int id = in ? p.tgt_i[(size_t)eu * p.T + es] : 0;
+        tg_h[threadIdx.x] = s == s ? rk_okey(s) : 0xffffffffu;
+        tg_l[threadIdx.x] = s == s ? rk_ikey(id) : 0xffffffffu;
+      }
+    }
     for (int sl = 0; sl < nsteps; ++sl) {
       const int st = news_step(sl);
       f32x16 acc[NR][2];
@@ -758,17 +820,19 @@ __global__ __launch_bounds__(kThreads) void rk_fused(RkParams p) {
           asm volatile("" : "+v"(nid[0]), "+v"(nid[1]));
           if (c == 0) {
             const int lane = fresh_lane();
+            // (pair form: the list of the user being COMPUTED, tile ti)
+            const int32_t* ids = MODE == kPair ? p.ids + (size_t)ti * p.M : p.ids;
 #pragma unroll
             for (int nt = 0; nt < 2; ++nt) {
               const int pos = st * kNT + 64 * nsub + 32 * nt + (lane & 31);
-              const int id = p.ids[min(pos, p.M - 1)];
+              const int id = ids[min(pos, p.M - 1)];
               nid[nt] = pos < p.M && (unsigned)id < (unsigned)N ? id : -1;
             }
           }
         }
         // the previous step's staged candidates (its epilogue is behind this barrier); the next
         // epilogue reads the list only after this chunk's barriers
-        if (c == 0 && sl > 0 && merger && !(MINER_RK_ABL & 4)) merge((sl - 1) & 1);
+        if (MODE == kRank && c == 0 && sl > 0 && merger && !(MINER_RK_ABL & 4)) merge((sl - 1) & 1);
         const bool pre = !(MINER_RK_ABL & 1) && q + PD < total_chunks;
         const int lane = fresh_lane();
         const int r = lane & 31, h = lane >> 5;
@@ -814,8 +878,8 @@ __global__ __launch_bounds__(kThreads) void rk_fused(RkParams p) {
         const int lane = fresh_lane();
         const int r = lane & 31, h = lane >> 5;
         const int user = ti * kUT + uu;
-        const float th_s = cnt[uu] < p.topk ? -INFINITY : list_s[uu * kMaxTopk + p.topk - 1];
-        const int th_i = cnt[uu] < p.topk ? 0x7fffffff : list_i[uu * kMaxTopk + p.topk - 1];
+        const float th_s = (MODE != kRank || cnt[uu] < p.topk) ? -INFINITY : list_s[uu * kMaxTopk + p.topk - 1];
+        const int th_i = (MODE != kRank || cnt[uu] < p.topk) ? 0x7fffffff : list_i[uu * kMaxTopk + p.topk - 1];
 #pragma unroll
         for (int nt = 0; nt < 2; ++nt) {
           // the candidate's identity: its table row (SUB: of this position's id, -1 for "none")
@@ -863,6 +927,36 @@ __global__ __launch_bounds__(kThreads) void rk_fused(RkParams p) {
                 if (32 * kt + 16 * h + e < K) sm += acc[kt][nt][e];
             score = xor32_sum(sm) / (float)K;            // model.py:130-131
           }
+          if constexpr (MODE == kCount) {
+            // Lane j holds the key of target j of user uu (a slot past T: the greatest key); lanes
+            // 0..31 hold the scores of news n0 + lane. The 32 score keys are broadcast in turn
+            // (v_readlane) and every lane compares each with its own target — one 64-bit compare and
+            // one add per (score, target) pair: T comparisons per score in one pass, whatever T (the
+            // kernel is issue-bound: as three float / int compares behind a liveness branch the same
+            // loop ran the config-5 call in 88.9 ms against 85.7, profiles/rk_rankof_ab.txt). A row
+            // past N (a clamped copy of row N - 1), an
+            // ineligible news and a NaN score take the key half 0, below every target's; a target
+            // never counts itself (a key is not greater than itself). The eligibility word of
+            // these 32 news is inside the bitmap whenever one of them is < N.
+            const int n0 = st * kNT + 64 * nsub + 32 * nt;
+            // (a scalar load: a vector load here is waited with vmcnt(0), behind the next chunk's DMAs
+            // in flight, and with or without a bitmap — the wait follows the join of the branch)
+            unsigned okw = 0xffffffffu;
+            if (p.ok != nullptr) okw = n0 < N ? rk_sload(p.ok + __builtin_amdgcn_readfirstlane(n0 >> 5)) : 0u;
+            const unsigned kh = n < N && ((okw >> r) & 1u) && score == score ? rk_okey(score) : 0u;   // 0: below every target
+            const unsigned long long kt = ((unsigned long long)tg_h[uu * kMaxT + lane] << 32) | tg_l[uu * kMaxT + lane];
+#pragma unroll
+            for (int i = 0; i < 32; ++i) {
+              const unsigned long long ki = ((unsigned long long)__builtin_amdgcn_readlane(kh, i) << 32) | rk_ikey(n0 + i);
+              tcount += ki > kt ? 1 : 0;
+            }
+            continue;
+          } else if constexpr (MODE == kPair) {
+            // both uu halves hold this user's scores: the first stores (n < 0: an id outside [0, N))
+            const int pos = st * kNT + 64 * nsub + 32 * nt + r;
+            if (uu == 0 && h == 0 && pos < p.M) p.top_s[(size_t)ti * p.M + pos] = n >= 0 ? score : -INFINITY;
+            continue;
+          }
           bool cand = h == 0 && (SUB ? n >= 0 : n < N) && user < p.U && better(score, n, th_s, th_i);
           unsigned long long bal = __ballot(cand);
           // the filters, on the few half-waves with an entry past the threshold: the eligibility
@@ -907,8 +1001,20 @@ __global__ __launch_bounds__(kThreads) void rk_fused(RkParams p) {
       // the staged candidates are merged at the next step's first chunk (merge, above), the last
       // step's below
     }
-    // ---- this tile's users are done: merge the last step, write their top-k ----
-    {
+    // ---- this tile's users are done ----
+    if constexpr (MODE == kCount) {
+      // the four nsub waves' counts of a user, summed by its first wave; counts[user][0..T) in one
+      // store. The second barrier: the next tile's targets and partial counts overwrite these.
+      const int lane = fresh_lane();
+      part[wave * kMaxT + lane] = tcount;
+      __syncthreads();
+      const int user = ti * kUT + uu;
+      if (nsub == 0 && user < p.U && lane < p.T) {
+        const int* pu = part + 4 * uu * kMaxT + lane;
+        p.top_i[(size_t)user * p.T + lane] = (pu[0] + pu[kMaxT]) + (pu[2 * kMaxT] + pu[3 * kMaxT]);
+      }
+      __syncthreads();
+    } else if constexpr (MODE == kRank) {   // merge the last step, write their top-k
       __syncthreads();
       if (merger && !(MINER_RK_ABL & 4)) merge((nsteps - 1) & 1);
       __syncthreads();
@@ -1169,6 +1275,52 @@ int rk_launch(void* stream, const RkParams& prm) {
   return flt ? rk_launch_geo<T, NKT, S, 0, true>(stream, prm, split) : rk_launch_geo<T, NKT, S, 0, false>(stream, prm, split);
 }
 
+// the counting and pair forms (MODE kCount / kPair): unsplit, GEO 0, the chunk count and K
+// compile-time by rk_launch_geo's rule (d = 768, and K = 64, in 16-bit) — a pair's score has the
+// bits of the ranking form that the same shape launches
+template <class T, int NKT, int S, int MODE>
+int rk_launch_form(void* stream, const RkParams& prm) {
+  constexpr bool P = MODE == kPair;              // the pair form gathers: SUB (and so FLT)
+  void (*kern)(RkParams) = rk_fused<T, NKT, S, 0, 1, 0, 0, P, P, MODE>;
+  if constexpr (sizeof(T) == 2) {
+    constexpr int kN768 = 768 * 2 / kRB<0>;
+    if (prm.d == 768) {
+      kern = rk_fused<T, NKT, S, kN768, 1, 0, 0, P, P, MODE>;
+      if constexpr (NKT == 2)
+        if (prm.K == 64) kern = rk_fused<T, NKT, S, kN768, 1, 0, 64, P, P, MODE>;
+    }
+  }
+  constexpr int NR = S == MINER_SCORE_WEIGHTED ? 2 * NKT : NKT;
+  const int lds = RkLds<NR, 0, P>::kTotal;
+  hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+  if (e != hipSuccess) return (int)e;
+  const int ntiles = P ? prm.U : (prm.U + kUT - 1) / kUT;
+  const int grid = num_cus() < ntiles ? num_cus() : ntiles;
+  hipLaunchKernelGGL(kern, dim3(grid), dim3(kThreads), lds, static_cast<hipStream_t>(stream), prm);
+  e = hipGetLastError();
+  return e == hipSuccess ? MINER_OK : (int)e;
+}
+
+template <class T, int MODE>
+int rk_dispatch_form(void* stream, const RkParams& prm) {
+  const int st = prm.score_type;
+  if (prm.K <= 32) {
+    if (st == MINER_SCORE_WEIGHTED) return rk_launch_form<T, 1, MINER_SCORE_WEIGHTED, MODE>(stream, prm);
+    if (st == MINER_SCORE_MAX) return rk_launch_form<T, 1, MINER_SCORE_MAX, MODE>(stream, prm);
+    return rk_launch_form<T, 1, MINER_SCORE_MEAN, MODE>(stream, prm);
+  }
+  if (st == MINER_SCORE_WEIGHTED) return rk_launch_form<T, 2, MINER_SCORE_WEIGHTED, MODE>(stream, prm);
+  if (st == MINER_SCORE_MAX) return rk_launch_form<T, 2, MINER_SCORE_MAX, MODE>(stream, prm);
+  return rk_launch_form<T, 2, MINER_SCORE_MEAN, MODE>(stream, prm);
+}
+
+template <int MODE>
+int rk_run_form(void* stream, int dtype, const RkParams& prm) {
+  if (dtype == MINER_DTYPE_BF16) return rk_dispatch_form<__bf16, MODE>(stream, prm);
+  if (dtype == MINER_DTYPE_F16) return rk_dispatch_form<_Float16, MODE>(stream, prm);
+  return rk_dispatch_form<float, MODE>(stream, prm);
+}
+
 template <class T>
 int rk_dispatch(void* stream, const RkParams& prm) {
   const int st = prm.score_type;
@@ -1233,9 +1385,53 @@ int rk_run(void* stream, int dtype, int score_type, const void* user_mui, const 
   return rk_dispatch<float>(stream, prm);
 }
 
+// the checks that miner_score_pairs and miner_rank_count share with rk_run, in its order and with
+// its codes (what they have no argument for — topk, the lists — left out)
+int rk_check_common(int dtype, int score_type, const void* user_mui, const void* user_proj, const void* news, int U, int N,
+                    int d, int K) {
+  const int ck = check_dims(dtype, d, 1, K);
+  if (ck != MINER_OK) return ck;
+  if (score_type < MINER_SCORE_WEIGHTED || score_type > MINER_SCORE_MEAN) return MINER_EINVAL;
+  if (U < 0 || N <= 0) return MINER_EINVAL;
+  if (!user_mui || !news) return MINER_EINVAL;
+  if (score_type == MINER_SCORE_WEIGHTED && !user_proj) return MINER_EINVAL;
+  if (!aligned16(user_mui) || !aligned16(user_proj) || !aligned16(news)) return MINER_EALIGN;
+  return MINER_OK;
+}
+
 }  // namespace
 
 extern "C" {
+
+int miner_score_pairs(void* stream, int dtype, int score_type, const void* user_mui, const void* user_proj,
+                      const void* news, int U, int N, int d, int K, const int32_t* cand_ids, int C, float* scores) {
+  const int ck = rk_check_common(dtype, score_type, user_mui, user_proj, news, U, N, d, K);
+  if (ck != MINER_OK) return ck;
+  if (C < 0 || (C > 0 && (!cand_ids || !scores))) return MINER_EINVAL;
+  if (!aligned4(cand_ids) || !aligned4(scores)) return MINER_EALIGN;
+  if (U == 0 || C == 0) return MINER_OK;
+  RkParams prm{};
+  prm.mui = user_mui; prm.proj = user_proj; prm.news = news; prm.top_s = scores;
+  prm.U = U; prm.N = N; prm.d = d; prm.K = K; prm.score_type = score_type;
+  prm.ids = cand_ids; prm.M = C;
+  return rk_run_form<kPair>(stream, dtype, prm);
+}
+
+int miner_rank_count(void* stream, int dtype, int score_type, const void* user_mui, const void* user_proj,
+                     const void* news, int U, int N, int d, int K, const float* target_scores, const int32_t* target_ids,
+                     int T, const uint32_t* news_ok, int32_t* counts) {
+  const int ck = rk_check_common(dtype, score_type, user_mui, user_proj, news, U, N, d, K);
+  if (ck != MINER_OK) return ck;
+  if (T <= 0 || !target_scores || !target_ids || !counts) return MINER_EINVAL;
+  if (T > kMaxT) return MINER_ESHAPE;
+  if (!aligned4(target_scores) || !aligned4(target_ids) || !aligned4(news_ok) || !aligned4(counts)) return MINER_EALIGN;
+  if (U == 0) return MINER_OK;
+  RkParams prm{};
+  prm.mui = user_mui; prm.proj = user_proj; prm.news = news; prm.top_i = counts;
+  prm.U = U; prm.N = N; prm.d = d; prm.K = K; prm.score_type = score_type;
+  prm.ok = news_ok; prm.tgt_s = target_scores; prm.tgt_i = target_ids; prm.T = T;
+  return rk_run_form<kCount>(stream, dtype, prm);
+}
 
 size_t miner_encoder_packed_bytes(int dtype, int d, int Dc, int K) {
   if (check_dims(dtype, d, Dc, K) != MINER_OK) return 0;
