@@ -22,6 +22,9 @@
  *   miner_score_pairs(...)    the click score of given (user, news) pairs, with the ranker's bits, and
  *   miner_rank_count(...)     per user and target (score, id), how many news rank before it: exact
  *                             full-corpus ranks, still without the U x N matrix.
+ *   miner_rank_topk_biased(...), miner_score_pairs_biased(...), miner_rank_count_biased(...)
+ *                             the ranking, pair and counting forms with a per-news fp32 prior added
+ *                             to the click score before it is used.
  *
  * Conventions are those of miner_score.h. dtype: MINER_DTYPE_F32 (exact fp32, parity mode),
  * MINER_DTYPE_BF16 or MINER_DTYPE_F16 (16-bit operands, fp32 accumulation and softmax).
@@ -192,6 +195,52 @@ int miner_score_pairs(void* stream, int dtype, int score_type, const void* user_
 int miner_rank_count(void* stream, int dtype, int score_type, const void* user_mui, const void* user_proj,
                      const void* news, int U, int N, int d, int K, const float* target_scores,
                      const int32_t* target_ids, int T, const uint32_t* news_ok, int32_t* counts);
+
+/*
+ * Score priors applied at rank time: the three forms above with a per-news fp32 prior added to the
+ * click score (recency decay, popularity, an editorial boost, a per-edition weight — whatever the
+ * feed adds before it ranks; the table may change between any two calls).
+ *   news_bias   [G, N] fp32, row-major, G >= 1: the prior of news n for the users of group g at
+ *               news_bias[g * N + n].
+ *   user_group  [U] int32, user u's row of news_bias, or NULL for "row 0 for every user". A value
+ *               outside [0, G) is the caller's error; the device clamps it into [0, G), so no
+ *               address leaves the table, and the result is then that of the clamped row.
+ * For user u and table row n every form uses
+ *   biased(u, n) = fp32_add_rn(score(u, n), news_bias[group(u)][n])
+ * where score(u, n) is exactly the fp32 value the unbiased form computes and the add is one separate
+ * IEEE addition (never contracted into the divide before it), so "scores + prior" in fp32 on any
+ * IEEE machine reproduces it bit for bit. The biased value is what is compared, listed, returned,
+ * counted against and stored; everything else — ties by the lower id, exclusion lists, the bitmap,
+ * subset ids, (-inf, -1) past N, -inf for a pair id outside [0, N) (no prior is read for it) —
+ * applies to the table id as before. A prior is not a filter: a -inf prior still lists the news
+ * while a list is not full (use news_ok to remove it); a +inf prior ranks it first (ties among
+ * them by id); a NaN sum is never listed or counted. Split and unsplit forms agree bit for bit.
+ *
+ * miner_rank_topk_biased: miner_rank_topk_subset's arguments, then the three above. news_ids NULL
+ * with M < 0 selects the whole table (miner_rank_topk_filtered); otherwise the subset rules hold.
+ * miner_score_pairs_biased / miner_rank_count_biased: miner_score_pairs / miner_rank_count plus the
+ * three; target_scores are biased scores (miner_score_pairs_biased's, for exact ranks).
+ * With news_bias NULL (and user_group NULL) each returns exactly what the unbiased call returns: it
+ * launches the same kernel. After the unbiased call's own argument checks, in their order and with
+ * their codes: news_bias non-NULL with G <= 0, or news_bias NULL with a non-NULL user_group:
+ * MINER_EINVAL; a news_bias, then a user_group, that is not 4-byte aligned: MINER_EALIGN (all
+ * before any launch, and before the U == 0 / C == 0 returns).
+ */
+int miner_rank_topk_biased(void* stream, int dtype, int score_type, const void* user_mui,
+                           const void* user_proj, const void* news, int U, int N, int d, int K, int topk,
+                           const int32_t* exclude_ids, int E, const uint32_t* news_ok,
+                           const int32_t* news_ids, int M, float* top_scores, int32_t* top_ids,
+                           void* workspace, size_t workspace_bytes, const float* news_bias, int G,
+                           const int32_t* user_group);
+int miner_score_pairs_biased(void* stream, int dtype, int score_type, const void* user_mui,
+                             const void* user_proj, const void* news, int U, int N, int d, int K,
+                             const int32_t* cand_ids, int C, float* scores, const float* news_bias, int G,
+                             const int32_t* user_group);
+int miner_rank_count_biased(void* stream, int dtype, int score_type, const void* user_mui,
+                            const void* user_proj, const void* news, int U, int N, int d, int K,
+                            const float* target_scores, const int32_t* target_ids, int T,
+                            const uint32_t* news_ok, int32_t* counts, const float* news_bias, int G,
+                            const int32_t* user_group);
 
 #ifdef __cplusplus
 }

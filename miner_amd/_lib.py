@@ -54,6 +54,10 @@ SIGNATURES = {
     "miner_topk_merge": (_I, [_P, _P, _P, _I, _P, _P, _I, _I, _I, _P, _I, _P, _P]),
     "miner_score_pairs": (_I, [_P, _I, _I, _P, _P, _P, _I, _I, _I, _I, _P, _I, _P]),
     "miner_rank_count": (_I, [_P, _I, _I, _P, _P, _P, _I, _I, _I, _I, _P, _P, _I, _P, _P]),
+    "miner_rank_topk_biased": (_I, [_P, _I, _I, _P, _P, _P, _I, _I, _I, _I, _I, _P, _I, _P, _P, _I, _P, _P, _P,
+                                    ctypes.c_size_t, _P, _I, _P]),
+    "miner_score_pairs_biased": (_I, [_P, _I, _I, _P, _P, _P, _I, _I, _I, _I, _P, _I, _P, _P, _I, _P]),
+    "miner_rank_count_biased": (_I, [_P, _I, _I, _P, _P, _P, _I, _I, _I, _I, _P, _P, _I, _P, _P, _P, _I, _P]),
     # include/miner_news.h
     "miner_news_precompute": (_I, [_P, _I, _P, _I, _P, _I, _I, _I, _P, _P]),
     "miner_score_news": (_I, [_P, _I, _I, _P, _P, _P, _I, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P]),

@@ -120,6 +120,7 @@ def build_library(force: bool = False, verbose: bool = False, debug: bool = Fals
 ASAN_DRIVER = os.path.join(ROOT, "tests", "native", "abi_errors.cpp")
 ASAN_DRIVER_SUBSET = os.path.join(ROOT, "tests", "native", "abi_errors_subset.cpp")
 ASAN_DRIVER_RANK = os.path.join(ROOT, "tests", "native", "abi_errors_rank.cpp")
+ASAN_DRIVER_BIAS = os.path.join(ROOT, "tests", "native", "abi_errors_bias.cpp")
 
 
 def build_asan_driver(force: bool = False, verbose: bool = False, driver: str = ASAN_DRIVER) -> str:
@@ -177,10 +178,18 @@ def build_asan_driver_rank(force: bool = False, verbose: bool = False) -> str:
     return build_asan_driver(force=force, verbose=verbose, driver=ASAN_DRIVER_RANK)
 
 
+def build_asan_driver_bias(force: bool = False, verbose: bool = False) -> str:
+    """build/asan/abi_errors_bias: the error paths of miner_rank_topk_biased, miner_score_pairs_biased
+    and miner_rank_count_biased (tests/native/abi_errors_bias.cpp; run by
+    tests/test_corpus_bias_host.py)."""
+    return build_asan_driver(force=force, verbose=verbose, driver=ASAN_DRIVER_BIAS)
+
+
 if __name__ == "__main__":
     if "--asan" in sys.argv:
         print(build_asan_driver(force="--force" in sys.argv, verbose=True))
         print(build_asan_driver_subset(verbose=True))
         print(build_asan_driver_rank(verbose=True))
+        print(build_asan_driver_bias(verbose=True))
     else:
         print(build_library(force="--force" in sys.argv, verbose=True, debug="--debug" in sys.argv))

@@ -12,6 +12,9 @@ d=768, fp16), backed by libminer_hip.so (include/miner_corpus.h).
     per_user, means = corpus_metrics(ranks, n_ranked)      # recall@k / hit@k / ndcg@k / mrr / auc
     ranks, metrics = evaluate_corpus(news_table, his_ids, his_mask, packed, clicked)  # the full-ranking protocol
     lists = rescore_topk(lists, new_mui, new_proj, news_table)    # served lists after the users changed
+    rank_topk(..., news_bias=prior)                        # fp32 [N] or [G, N] (+ user_group [U]) added to the
+                                                           # click score before it ranks; also score_pairs, rank_of,
+                                                           # update_topk, rescore_topk, rank_corpus, evaluate_corpus
 
 The click score of (user, news) is the reference's (src/model/model.py:127-134, 213-214) with the
 impression's candidate set replaced by the whole news table; ties rank the lower news id first.
@@ -170,9 +173,53 @@ def _news_id_list(news_ids, N: int) -> NewsIdList:
     return canonical_news_ids(news_ids, N)
 
 
+@dataclasses.dataclass
+class _Prior:
+    """A checked score prior: bias fp32 [G, N] contiguous on the device, group int32 [U] or None
+    (every user reads row 0)."""
+    bias: Tensor
+    group: Optional[Tensor]
+
+    @property
+    def G(self) -> int:
+        return self.bias.shape[0]
+
+    def users(self, u0: int, u1: int) -> "_Prior":
+        return _Prior(self.bias, None if self.group is None else self.group[u0:u1])
+
+
+def _prior(news_bias, user_group, U: int, N: int) -> Optional[_Prior]:
+    """news_bias= / user_group= of the ranking entries -> a _Prior, or None without a prior. Shapes,
+    dtypes and the group values are checked before anything touches the device."""
+    if isinstance(news_bias, _Prior):
+        if user_group is not None:
+            raise ValueError("user_group is part of the checked prior")
+        return news_bias
+    if news_bias is None:
+        if user_group is not None:
+            raise ValueError("user_group without news_bias")
+        return None
+    if not isinstance(news_bias, Tensor) or news_bias.dtype != torch.float32 or news_bias.dim() not in (1, 2) \
+            or news_bias.shape[-1] != N or news_bias.shape[0] < 1:
+        raise ValueError(f"news_bias must be a float32 [{N}] or [G, {N}] tensor")
+    G = 1 if news_bias.dim() == 1 else news_bias.shape[0]
+    if user_group is None:
+        if G > 1:
+            raise ValueError(f"news_bias holds {G} rows: user_group [{U}] says which row a user reads")
+    else:
+        if not isinstance(user_group, Tensor) or user_group.dim() != 1 or user_group.shape[0] != U \
+                or user_group.is_floating_point() or user_group.is_complex() or user_group.dtype == torch.bool:
+            raise ValueError(f"user_group must be an integer [{U}] tensor")
+        if U and (int(user_group.min()) < 0 or int(user_group.max()) >= G):
+            raise ValueError(f"user_group out of range [0, {G})")
+    _require_device(news_bias, user_group)
+    return _Prior(news_bias.reshape(G, N).contiguous(), _contig(user_group, torch.int32))
+
+
 def rank_topk(user_mui: Tensor, user_proj: Optional[Tensor], news: Tensor, topk: int, *,
               score_type: str = "weighted", exclude_ids: Optional[Tensor] = None,
-              eligible: Optional[Tensor] = None, news_ids=None):
+              eligible: Optional[Tensor] = None, news_ids=None, news_bias=None,
+              user_group: Optional[Tensor] = None):
     """Top-k news per user by the click score, best first: (scores [U,topk] fp32, ids [U,topk]
     int32); entries past the table size are (-inf, -1).
 
@@ -187,7 +234,17 @@ def rank_topk(user_mui: Tensor, user_proj: Optional[Tensor], news: Tensor, topk:
     ``eligible`` given too: the intersection), which streams the whole table whatever it holds.
     Measured on 2,048 users x 200,000 news (fp16, K = 64, d = 768, profiles/rk_subset_ab.txt): 1 % of
     the table 0.021x, 5 % 0.064x, 25 % 0.270x, 100 % 1.024x the bitmap form's 78 ms — the bitmap form
-    is the faster one only above M/N of about 0.98. Nothing reroutes an ``eligible=`` call: the caller chooses the form."""
+    is the faster one only above M/N of about 0.98. Nothing reroutes an ``eligible=`` call: the caller chooses the form.
+
+    news_bias: a score prior, float32 [N] or [G, N] on the device (recency, popularity, an editorial
+    boost, a per-edition weight), with user_group an integer [U] tensor of rows in [0, G) (required
+    when G > 1). The list is ranked by fp32(score + news_bias[user_group[u], n]) — one IEEE add on the
+    unbiased score, so ``scores + prior`` in torch fp32 reproduces it bit for bit — and that sum is
+    the score returned. Filters, ties (lower id first) and ``news_ids`` work on the table id as
+    before. A prior is not a filter: a -inf prior still lists the news while a list has room (use
+    ``eligible``); +inf ranks it first; a NaN sum is never listed. Without news_bias the call is
+    today's."""
+    pri = _prior(news_bias, user_group, user_mui.shape[0], news.shape[0])
     st = _lib.SCORE_TYPES.get(score_type)
     if st is None or st == _lib.SCORE_NONE:
         raise ValueError("Invalid method of aggregating matching score")  # model.py:136
@@ -228,7 +285,13 @@ def rank_topk(user_mui: Tensor, user_proj: Optional[Tensor], news: Tensor, topk:
     nws = int(lib.miner_rank_topk_workspace_bytes(U, topk)) if split else 0
     ws = torch.empty(nws, dtype=torch.uint8, device=dev) if nws else None
     with torch.cuda.device(dev):
-        if sub is not None:
+        if pri is not None:
+            M = -1 if sub is None else sub.ids.numel()       # -1 with no list: the whole table
+            rc = lib.miner_rank_topk_biased(_stream(dev), dt, st, _ptr(mui), _ptr(proj), _ptr(tab), U, N, d, K, topk,
+                                            _ptr(excl), E, _ptr(ok), _ptr(sub.ids) if M > 0 else None, M,
+                                            _ptr(top_s), _ptr(top_i), _ptr(ws), nws, _ptr(pri.bias), pri.G,
+                                            _ptr(pri.group))
+        elif sub is not None:
             rc = lib.miner_rank_topk_subset(_stream(dev), dt, st, _ptr(mui), _ptr(proj), _ptr(tab), U, N, d, K, topk,
                                             _ptr(excl), E, _ptr(ok), _ptr(sub.ids) if sub.ids.numel() else None,
                                             sub.ids.numel(), _ptr(top_s), _ptr(top_i), _ptr(ws), nws)
@@ -296,19 +359,22 @@ def merge_topk(a, b, topk: Optional[int] = None, *, eligible: Optional[Tensor] =
 
 def update_topk(lists, user_mui: Tensor, user_proj: Optional[Tensor], news: Tensor, news_ids, *,
                 score_type: str = "weighted", exclude_ids: Optional[Tensor] = None,
-                eligible: Optional[Tensor] = None):
+                eligible: Optional[Tensor] = None, news_bias=None, user_group: Optional[Tensor] = None):
     """Incremental ranking: ``lists`` = (scores [U,k], ids [U,k]) ranked earlier for these users; the
     table rows ``news_ids`` (new or changed news) are ranked with rank_topk(news_ids=...) and merged
     in with merge_topk — a re-ranked news takes its fresh score. ``exclude_ids`` filters the fresh
     rows as in rank_topk; ``eligible`` filters them and also prunes expired news from ``lists``.
-    Returns the new (scores [U,k], ids [U,k]); the cost follows len(news_ids), not the table."""
+    Returns the new (scores [U,k], ids [U,k]); the cost follows len(news_ids), not the table.
+    ``news_bias`` / ``user_group`` as in rank_topk: the fresh rows are ranked under the prior that
+    ``lists`` was ranked under (a list ranked under another prior holds stale scores: rescore_topk)."""
+    pri = _prior(news_bias, user_group, user_mui.shape[0], news.shape[0])
     old = _list_pair(lists, "lists")
     k = old[0].shape[1]
     if k < 1:
         raise ValueError("lists must hold at least one entry per user")
     ok = None if eligible is None else _eligible_words(eligible, news.shape[0])
     fresh = rank_topk(user_mui, user_proj, news, k, score_type=score_type, exclude_ids=exclude_ids, eligible=ok,
-                      news_ids=news_ids)
+                      news_ids=news_ids, news_bias=pri)
     return merge_topk(old, fresh, k, eligible=ok)
 
 
@@ -354,7 +420,7 @@ def _bits_at(words: Tensor, ids: Tensor) -> Tensor:
     return (((words[safe >> 5].to(torch.int64) >> (safe & 31)) & 1) != 0) & (ids >= 0)
 
 
-def _score_pairs(st, dt, mui, proj, tab, ids64: Tensor) -> Tensor:
+def _score_pairs(st, dt, mui, proj, tab, ids64: Tensor, pri: Optional[_Prior] = None) -> Tensor:
     U, K, d = mui.shape
     C = ids64.shape[1]
     out = torch.empty(U, C, dtype=torch.float32, device=mui.device)
@@ -362,22 +428,29 @@ def _score_pairs(st, dt, mui, proj, tab, ids64: Tensor) -> Tensor:
         return out
     ids = ids64.to(torch.int32).contiguous()
     with torch.cuda.device(mui.device):
-        rc = _lib.lib().miner_score_pairs(_stream(mui.device), dt, st, _ptr(mui), _ptr(proj), _ptr(tab), U, tab.shape[0],
-                                          d, K, _ptr(ids), C, _ptr(out))
+        if pri is not None:
+            rc = _lib.lib().miner_score_pairs_biased(_stream(mui.device), dt, st, _ptr(mui), _ptr(proj), _ptr(tab), U,
+                                                     tab.shape[0], d, K, _ptr(ids), C, _ptr(out), _ptr(pri.bias),
+                                                     pri.G, _ptr(pri.group))
+        else:
+            rc = _lib.lib().miner_score_pairs(_stream(mui.device), dt, st, _ptr(mui), _ptr(proj), _ptr(tab), U,
+                                              tab.shape[0], d, K, _ptr(ids), C, _ptr(out))
     _lib.check(rc, "miner_score_pairs")
     return out
 
 
 def score_pairs(user_mui: Tensor, user_proj: Optional[Tensor], news: Tensor, cand_ids: Tensor, *,
-                score_type: str = "weighted") -> Tensor:
+                score_type: str = "weighted", news_bias=None, user_group: Optional[Tensor] = None) -> Tensor:
     """The click score of chosen pairs: scores[u, c] of (user u, news[cand_ids[u, c]]), fp32 [U, C] —
     bit for bit what rank_topk computes for that pair, from the cached user vectors. cand_ids [U, C]
     of any integer dtype, any order, repeats allowed; an id outside [0, N) (a -1 padding) gives -inf.
     Only the U x C rows are read: the second stage of a recommender, or the refresh of a served list
-    (rescore_topk)."""
+    (rescore_topk). ``news_bias`` / ``user_group`` as in rank_topk: the prior of the pair's news is
+    added (an id outside [0, N) stays -inf)."""
     _check_ids(cand_ids, user_mui.shape[0], "cand_ids")
+    pri = _prior(news_bias, user_group, user_mui.shape[0], news.shape[0])
     st, dt, mui, proj, tab = _rank_operands(user_mui, user_proj, news, score_type)
-    return _score_pairs(st, dt, mui, proj, tab, _id_matrix(cand_ids, mui.shape[0], tab.shape[0], "cand_ids"))
+    return _score_pairs(st, dt, mui, proj, tab, _id_matrix(cand_ids, mui.shape[0], tab.shape[0], "cand_ids"), pri)
 
 
 def _better(s: Tensor, i: Tensor, s2: Tensor, i2: Tensor) -> Tensor:
@@ -385,7 +458,7 @@ def _better(s: Tensor, i: Tensor, s2: Tensor, i2: Tensor) -> Tensor:
     return (s > s2) | ((s == s2) & (i < i2))
 
 
-def _rank_of(user_mui, user_proj, news, target_ids, score_type, exclude_ids, eligible):
+def _rank_of(user_mui, user_proj, news, target_ids, score_type, exclude_ids, eligible, news_bias=None, user_group=None):
     _check_ids(target_ids, user_mui.shape[0], "target_ids")
     if not 1 <= target_ids.shape[1] <= MAX_TARGETS:
         raise ValueError(f"target_ids holds {target_ids.shape[1]} targets per user, outside [1, {MAX_TARGETS}]")
@@ -393,6 +466,7 @@ def _rank_of(user_mui, user_proj, news, target_ids, score_type, exclude_ids, eli
         _check_ids(exclude_ids, user_mui.shape[0], "exclude_ids")
         if exclude_ids.shape[1] > MAX_L:
             raise ValueError(f"exclude_ids holds {exclude_ids.shape[1]} ids per user, more than {MAX_L}")
+    pri = _prior(news_bias, user_group, user_mui.shape[0], news.shape[0])
     st, dt, mui, proj, tab = _rank_operands(user_mui, user_proj, news, score_type)
     U, K, d = mui.shape
     N = tab.shape[0]
@@ -406,13 +480,18 @@ def _rank_of(user_mui, user_proj, news, target_ids, score_type, exclude_ids, eli
         if ex.shape[1] == 0:
             ex = None
     ok = None if eligible is None else _eligible_words(eligible, N)
-    tgt_s = _score_pairs(st, dt, mui, proj, tab, tid)
+    tgt_s = _score_pairs(st, dt, mui, proj, tab, tid, pri)      # with a prior: biased, as the stream's scores are
     counts = torch.empty(U, T, dtype=torch.int32, device=dev)
     if U:
         tid32 = tid.to(torch.int32).contiguous()
         with torch.cuda.device(dev):
-            rc = _lib.lib().miner_rank_count(_stream(dev), dt, st, _ptr(mui), _ptr(proj), _ptr(tab), U, N, d, K,
-                                             _ptr(tgt_s), _ptr(tid32), T, _ptr(ok), _ptr(counts))
+            if pri is not None:
+                rc = _lib.lib().miner_rank_count_biased(_stream(dev), dt, st, _ptr(mui), _ptr(proj), _ptr(tab), U, N, d,
+                                                        K, _ptr(tgt_s), _ptr(tid32), T, _ptr(ok), _ptr(counts),
+                                                        _ptr(pri.bias), pri.G, _ptr(pri.group))
+            else:
+                rc = _lib.lib().miner_rank_count(_stream(dev), dt, st, _ptr(mui), _ptr(proj), _ptr(tab), U, N, d, K,
+                                                 _ptr(tgt_s), _ptr(tid32), T, _ptr(ok), _ptr(counts))
         _lib.check(rc, "miner_rank_count")
     appears = (tid >= 0) & ~torch.isnan(tgt_s)
     if ok is not None:
@@ -425,7 +504,7 @@ def _rank_of(user_mui, user_proj, news, target_ids, score_type, exclude_ids, eli
         # — their scores are the stream's own bits (score_pairs), so the correction is exact
         ex = torch.sort(ex, dim=1).values
         ex[:, 1:] = torch.where(ex[:, 1:] == ex[:, :-1], -1, ex[:, 1:])
-        ex_s = _score_pairs(st, dt, mui, proj, tab, ex)
+        ex_s = _score_pairs(st, dt, mui, proj, tab, ex, pri)
         live = ex >= 0 if ok is None else _bits_at(ok, ex)
         survivors -= live.sum(dim=1)
         E = ex.shape[1]
@@ -440,7 +519,8 @@ def _rank_of(user_mui, user_proj, news, target_ids, score_type, exclude_ids, eli
 
 
 def rank_of(user_mui: Tensor, user_proj: Optional[Tensor], news: Tensor, target_ids: Tensor, *,
-            score_type: str = "weighted", exclude_ids: Optional[Tensor] = None, eligible: Optional[Tensor] = None):
+            score_type: str = "weighted", exclude_ids: Optional[Tensor] = None, eligible: Optional[Tensor] = None,
+            news_bias=None, user_group: Optional[Tensor] = None):
     """Exact full-corpus ranks: (ranks int32 [U, T], scores fp32 [U, T]) for target_ids [U, T]
     (integer, T <= 64). ranks[u, j] is the 0-based position news target_ids[u, j] holds in user u's
     complete filtered list — what rank_topk with the same ``exclude_ids`` / ``eligible`` would return
@@ -448,8 +528,11 @@ def rank_of(user_mui: Tensor, user_proj: Optional[Tensor], news: Tensor, target_
     exclude_ids[u], or a NaN score). The table is streamed once for all T targets and no list is
     kept (miner_rank_count); the targets' scores come from score_pairs, whose bits are the stream's
     own, so the count is exact and a tie ranks by id. The exclusion list is a correction on the device:
-    its distinct, in-range, eligible ids that rank before the target are subtracted."""
-    ranks, scores, _ = _rank_of(user_mui, user_proj, news, target_ids, score_type, exclude_ids, eligible)
+    its distinct, in-range, eligible ids that rank before the target are subtracted. ``news_bias`` /
+    ``user_group`` as in rank_topk: targets, stream and correction all use the biased score, so the
+    rank is exact under the prior too (a target whose biased score is NaN gets -1)."""
+    ranks, scores, _ = _rank_of(user_mui, user_proj, news, target_ids, score_type, exclude_ids, eligible, news_bias,
+                                user_group)
     return ranks, scores
 
 
@@ -495,14 +578,17 @@ def corpus_metrics(ranks: Tensor, n_ranked: Optional[Tensor] = None, *, ks=(5, 1
 
 
 def rescore_topk(lists, user_mui: Tensor, user_proj: Optional[Tensor], news: Tensor, *,
-                 score_type: str = "weighted", eligible: Optional[Tensor] = None):
+                 score_type: str = "weighted", eligible: Optional[Tensor] = None, news_bias=None,
+                 user_group: Optional[Tensor] = None):
     """Served lists (scores [U,k], ids [U,k]) after the users' vectors changed: the lists' ids are
     scored again with score_pairs and re-sorted (and, with ``eligible``, pruned) by merge_topk. Returns
-    lists of the same width — for each user, rank_topk(news_ids=<its old ids>) bit for bit."""
+    lists of the same width — for each user, rank_topk(news_ids=<its old ids>) bit for bit, under the
+    prior ``news_bias`` / ``user_group`` if one is given (also the way to move a list to a new prior)."""
+    pri = _prior(news_bias, user_group, user_mui.shape[0], news.shape[0])
     _, ids = _list_pair(lists, "lists")
     if ids.shape[1] < 1:
         raise ValueError("lists must hold at least one entry per user")
-    fresh = score_pairs(user_mui, user_proj, news, ids, score_type=score_type)
+    fresh = score_pairs(user_mui, user_proj, news, ids, score_type=score_type, news_bias=pri)
     empty = (fresh[:, :0], ids[:, :0])
     return merge_topk(empty, (fresh, ids), ids.shape[1], eligible=eligible)
 
@@ -510,17 +596,20 @@ def rescore_topk(lists, user_mui: Tensor, user_proj: Optional[Tensor], news: Ten
 def evaluate_corpus(news: Tensor, his_ids: Tensor, his_mask: Tensor, packed: EncoderWeights, target_ids: Tensor, *,
                     ks=(5, 10), batch: int = 16384, exclude_history: bool = True,
                     exclude_ids: Optional[Tensor] = None, eligible: Optional[Tensor] = None,
-                    his_bias: Optional[Tensor] = None, score_type: str = "weighted"):
+                    his_bias: Optional[Tensor] = None, score_type: str = "weighted", news_bias=None,
+                    user_group: Optional[Tensor] = None):
     """The full-ranking evaluation protocol on one GPU's share of the users: rank_corpus's loop with
     rank_of in place of rank_topk. Every user is encoded from its history and each held-out click
     target_ids[u, j] (-1: no target in that slot) is ranked among all N news, the user's history
     (``exclude_history``) and ``exclude_ids`` left out, ``eligible`` as in rank_topk. Returns
     (ranks int32 [U, T], metrics): corpus_metrics' means — recall@k, hit@k, ndcg@k, mrr, auc. Each
-    user's ranks are independent of the batching."""
+    user's ranks are independent of the batching. ``news_bias`` / ``user_group`` [U] as in rank_topk
+    (checked once, sliced per batch): the ranks under the prior."""
     if batch <= 0:
         raise ValueError("batch must be positive")
     U = his_ids.shape[0]
     dev = news.device
+    pri = _prior(news_bias, user_group, U, news.shape[0])
     _require_device(news, his_ids, his_mask, target_ids, exclude_ids, eligible)
     excl = exclude_ids
     if excl is not None and (excl.dim() != 2 or excl.shape[0] != U):
@@ -541,14 +630,16 @@ def evaluate_corpus(news: Tensor, his_ids: Tensor, his_mask: Tensor, packed: Enc
         mui, proj = encode_users(news, his_mask[u0:u1], packed, his_ids=his_ids[u0:u1],
                                  his_bias=None if his_bias is None else his_bias[u0:u1], with_proj=with_proj)
         ranks[u0:u1], _, survivors[u0:u1] = _rank_of(mui, proj, news, target_ids[u0:u1], score_type,
-                                                     None if excl is None else excl[u0:u1], ok)
+                                                     None if excl is None else excl[u0:u1], ok,
+                                                     None if pri is None else pri.users(u0, u1))
     return ranks, corpus_metrics(ranks, survivors, ks=ks)[1]
 
 
 def rank_corpus(news: Tensor, his_ids: Tensor, his_mask: Tensor, packed: EncoderWeights, topk: int, *,
                 his_bias: Optional[Tensor] = None, score_type: str = "weighted", batch: int = 16384,
                 out: Optional[tuple] = None, exclude_history: bool = False, exclude_ids: Optional[Tensor] = None,
-                eligible: Optional[Tensor] = None, news_ids=None):
+                eligible: Optional[Tensor] = None, news_ids=None, news_bias=None,
+                user_group: Optional[Tensor] = None):
     """BASELINE config 5 on one GPU's share of the users: every user (his_ids [U,L] into the news
     table [N,d], his_mask [U,L]) encoded and ranked against the whole table, ``batch`` users per
     encode + rank pair so that the [batch,K,d] user vectors are all that is ever held (125,000 users
@@ -558,11 +649,12 @@ def rank_corpus(news: Tensor, his_ids: Tensor, his_mask: Tensor, packed: Encoder
 
     ``exclude_history`` keeps each user's own clicked news (the unmasked his_ids) out of its list,
     ``exclude_ids`` [U,E] further ids, together at most 256 per user; ``eligible`` and ``news_ids`` (rank only these table rows) as in
-    rank_topk."""
+    rank_topk; ``news_bias`` / ``user_group`` [U] (a score prior, checked once and sliced per batch) too."""
     if batch <= 0:
         raise ValueError("batch must be positive")
     U = his_ids.shape[0]
     dev = news.device
+    pri = _prior(news_bias, user_group, U, news.shape[0])
     _require_device(news, his_ids, his_mask, exclude_ids, eligible)
     excl = exclude_ids
     if excl is not None and (excl.dim() != 2 or excl.shape[0] != U):
@@ -582,7 +674,8 @@ def rank_corpus(news: Tensor, his_ids: Tensor, his_mask: Tensor, packed: Encoder
         mui, proj = encode_users(news, his_mask[u0:u1], packed, his_ids=his_ids[u0:u1],
                                  his_bias=None if his_bias is None else his_bias[u0:u1], with_proj=with_proj)
         s, i = rank_topk(mui, proj, news, topk, score_type=score_type,
-                         exclude_ids=None if excl is None else excl[u0:u1], eligible=ok, news_ids=sub)
+                         exclude_ids=None if excl is None else excl[u0:u1], eligible=ok, news_ids=sub,
+                         news_bias=None if pri is None else pri.users(u0, u1))
         top_s[u0:u1] = s
         top_i[u0:u1] = i
     return top_s, top_i

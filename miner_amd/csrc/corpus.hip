@@ -458,6 +458,9 @@ struct RkParams {
   const float* tgt_s;      // counting form: [U][T] target scores and ids; the counts go to top_i [U][T]
   const int32_t* tgt_i;
   int T;
+  const float* bias;       // BIAS: the score priors [G][N] fp32, added to every score before it is used
+  const int32_t* grp;      //       [U] prior rows (NULL: row 0 for every user), clamped into [0, G)
+  int G;
 };
 
 // S > 1 (S = 8, grid = 256): the news steps are dealt to S slices (step st of slice s is news step
@@ -561,13 +564,26 @@ struct RkLds {
 // user's own id list ids[u][0..M); the score goes to top_s[u][pos], -inf for an id outside [0, N).
 // The d-chunk loop, the K reductions and the lane-half exchanges are the ones of kRank, so a pair's
 // score has the same bits in all three.
+// BIAS: the biased forms (RkParams bias / grp / G; the ranking forms always with FLT, as SUB). The
+// score of (user u, news n) becomes fp32_add_rn(score, bias[group(u)][n]) — one separate IEEE add
+// (rk_add_rn) on the finished score — before the threshold test, the key compare or the store, so
+// lists, counts and pair scores agree bit for bit with "scores + prior" in fp32. A compile-time
+// switch for the reason FLT is one: the unbiased instantiations are the same code as without it.
 constexpr int kRank = 0, kCount = 1, kPair = 2;
 constexpr int kMaxT = MINER_CORPUS_MAX_TARGETS;
 
+// a + b rounded once to nearest even, never contracted with the operation that made a (the divide
+// of the mean and weighted scores): the compiler cannot see through the barrier
+__device__ __forceinline__ float rk_add_rn(float a, float b) {
+  asm volatile("" : "+v"(a));
+  return __fadd_rn(a, b);
+}
+
 template <class T, int NKT, int SCORE, int NCH = 0, int S = 1, int GEO = 0, int KC = 0, bool FLT = false,   // KC: K compile-time (0: run time)
-          bool SUB = false, int MODE = kRank>
+          bool SUB = false, int MODE = kRank, bool BIAS = false>
 __global__ __launch_bounds__(kThreads) void rk_fused(RkParams p) {
   static_assert(!SUB || (FLT && GEO == 0), "the subset form: a filtered form with one chunk in flight");
+  static_assert(!BIAS || (GEO == 0 && (FLT || MODE == kCount)), "the biased forms: GEO 0, the ranking forms filtered");
   static_assert(MODE == kRank || (S == 1 && GEO == 0 && SUB == (MODE == kPair)), "counting and pair forms: unsplit, GEO 0");
   static_assert(kMaxT == 64 && kUT * kMaxT * 8 <= kUT * kMaxTopk * 8 && kUT * 4 * kMaxT * 4 <= 2 * kUT * kNT * 8,
                 "one target per lane; the targets in the list area, the partial counts in the staging area");
@@ -778,6 +794,48 @@ __global__ __launch_bounds__(kThreads) void rk_fused(RkParams p) {
   }
   int q = 0;
   int nid[2] = {-1, -1};       // SUB: the table ids of this lane's news columns in the step being computed
+  // BIAS: the priors of those two news for user uu (0 where there is no news): pri in the step being
+  // computed, pnx in the step after it (the next tile's first step after a tile's last), loaded a
+  // step ahead — at a step's first chunk, when nothing of this wave is in flight — so that every path
+  // from the load to the epilogue that adds it passes a chunk's wait: issued in the epilogue, or
+  // used in the step that loads it, the load is waited with vmcnt(0) behind the row DMAs of the
+  // chunk in flight. The gathering forms load the next step's ids (idn) the same way and the priors
+  // at those ids one chunk later (a one-chunk step: at once, behind a wait of their own).
+  [[maybe_unused]] float pri[2] = {0.f, 0.f}, pnx[2] = {0.f, 0.f};
+  [[maybe_unused]] int idn[2] = {-1, -1};
+  [[maybe_unused]] const float* prow = nullptr;   // the prior row of pnx's user
+  // the prior row of the user in this wave's uu slot of tile t (the two users of a tile may read
+  // different rows); a user past U takes the last user's and a group outside [0, G) is clamped, so
+  // no address leaves the table
+  auto prior_row = [&](int t) -> const float* {
+    const int bu = min(MODE == kPair ? t : t * kUT + uu, p.U - 1);
+    int g = 0;
+    if (p.grp != nullptr) g = (int)rk_sload(reinterpret_cast<const uint32_t*>(p.grp) + bu);
+    return p.bias + (size_t)min(max(g, 0), p.G - 1) * (size_t)N;
+  };
+  auto load_idn = [&](int t, int s) {             // SUB: as nid, for slice step s of tile t
+    const int lane = fresh_lane();
+    const int32_t* ids = MODE == kPair ? p.ids + (size_t)t * p.M : p.ids;
+#pragma unroll
+    for (int nt = 0; nt < 2; ++nt) {
+      const int pos = news_step(s) * kNT + 64 * nsub + 32 * nt + (lane & 31);
+      const int id = ids[min(pos, p.M - 1)];
+      idn[nt] = pos < p.M && (unsigned)id < (unsigned)N ? id : -1;
+    }
+  };
+  auto load_pnx = [&](int s) {                    // one coalesced 128-byte load per (nt, user)
+    const int lane = fresh_lane();
+#pragma unroll
+    for (int nt = 0; nt < 2; ++nt) {
+      const int n = SUB ? idn[nt] : news_step(s) * kNT + 64 * nsub + 32 * nt + (lane & 31);
+      pnx[nt] = (SUB ? n >= 0 : n < N) ? prow[n] : 0.f;
+    }
+  };
+  if constexpr (BIAS) {                           // the first step's (complete behind the first chunk's wait)
+    prow = prior_row(first);
+    if constexpr (SUB) load_idn(first, 0);
+    load_pnx(0);
+  }
   for (int ti = first; ti < ntiles; ti += tstride) {
     // the tile's exclusion lists (the previous tile's epilogues are behind its closing barriers; this
     // tile's first epilogue comes after a chunk barrier). A user past U and slots past E hold -1.
@@ -828,6 +886,22 @@ __global__ __launch_bounds__(kThreads) void rk_fused(RkParams p) {
               const int id = ids[min(pos, p.M - 1)];
               nid[nt] = pos < p.M && (unsigned)id < (unsigned)N ? id : -1;
             }
+          }
+        }
+        if constexpr (BIAS) {
+          // what was loaded for the next step is complete behind the wait above (pinned, as the ids
+          // are); at a step's first chunk it becomes this step's, and the step after is loaded
+          asm volatile("" : "+v"(pnx[0]), "+v"(pnx[1]));
+          if constexpr (SUB) asm volatile("" : "+v"(idn[0]), "+v"(idn[1]));
+          if (c == 0) { pri[0] = pnx[0]; pri[1] = pnx[1]; }
+          const bool wrap = sl + 1 == nsteps;
+          const int t2 = wrap ? ti + tstride : ti, s2 = wrap ? 0 : sl + 1;
+          if (t2 < ntiles) {
+            if (c == 0) {
+              if (wrap) prow = prior_row(t2);
+              if constexpr (SUB) load_idn(t2, s2);
+            }
+            if (c == (SUB && nchunk > 1 ? 1 : 0)) load_pnx(s2);
           }
         }
         // the previous step's staged candidates (its epilogue is behind this barrier); the next
@@ -927,6 +1001,7 @@ __global__ __launch_bounds__(kThreads) void rk_fused(RkParams p) {
                 if (32 * kt + 16 * h + e < K) sm += acc[kt][nt][e];
             score = xor32_sum(sm) / (float)K;            // model.py:130-131
           }
+          if constexpr (BIAS) score = rk_add_rn(score, pri[nt]);
           if constexpr (MODE == kCount) {
             // Lane j holds the key of target j of user uu (a slot past T: the greatest key); lanes
             // 0..31 hold the scores of news n0 + lane. The 32 score keys are broadcast in turn
@@ -1224,19 +1299,22 @@ bool rk_split(const RkParams& prm) {
   return num_cus() == 256;
 }
 
-template <class T, int NKT, int S, int GEO, bool FLT, bool SUB = false>
+template <class T, int NKT, int S, int GEO, bool FLT, bool SUB = false, bool BIAS = false>
 int rk_launch_geo(void* stream, const RkParams& prm, bool split) {
   // d = 768 in 16-bit (config 5): the chunk count compile-time
-  void (*kern)(RkParams) = split ? rk_fused<T, NKT, S, 0, kSplit, GEO, 0, FLT, SUB> : rk_fused<T, NKT, S, 0, 1, GEO, 0, FLT, SUB>;
+  void (*kern)(RkParams) = split ? rk_fused<T, NKT, S, 0, kSplit, GEO, 0, FLT, SUB, kRank, BIAS>
+                                 : rk_fused<T, NKT, S, 0, 1, GEO, 0, FLT, SUB, kRank, BIAS>;
   if constexpr (sizeof(T) == 2) {
     // config 5's d = 768 and K = 64 compile-time (the masked interest loops of the epilogue compile
     // away; the top-k equals the oracle's at the 16-bit bar, tests/test_gpu_corpus.py)
     constexpr int kN768 = 768 * 2 / kRB<GEO>;
     if (prm.d == 768) {
       if (NKT == 2 && prm.K == 64)
-        kern = split ? rk_fused<T, NKT, S, kN768, kSplit, GEO, 64, FLT, SUB> : rk_fused<T, NKT, S, kN768, 1, GEO, 64, FLT, SUB>;
+        kern = split ? rk_fused<T, NKT, S, kN768, kSplit, GEO, 64, FLT, SUB, kRank, BIAS>
+                     : rk_fused<T, NKT, S, kN768, 1, GEO, 64, FLT, SUB, kRank, BIAS>;
       else
-        kern = split ? rk_fused<T, NKT, S, kN768, kSplit, GEO, 0, FLT, SUB> : rk_fused<T, NKT, S, kN768, 1, GEO, 0, FLT, SUB>;
+        kern = split ? rk_fused<T, NKT, S, kN768, kSplit, GEO, 0, FLT, SUB, kRank, BIAS>
+                     : rk_fused<T, NKT, S, kN768, 1, GEO, 0, FLT, SUB, kRank, BIAS>;
     }
   }
   constexpr int NR = S == MINER_SCORE_WEIGHTED ? 2 * NKT : NKT;
@@ -1263,6 +1341,10 @@ int rk_launch(void* stream, const RkParams& prm) {
   const bool flt = prm.ok != nullptr || prm.E > 0;     // the filtered instantiation only when asked for
   // the subset form: one instantiation per shape, the filtered one (either filter may be null),
   // with the chunk count and K chosen as for the table forms
+  // the biased forms: filtered (as the subset form, either filter may be null), GEO 0
+  if (prm.bias != nullptr)
+    return prm.ids != nullptr ? rk_launch_geo<T, NKT, S, 0, true, true, true>(stream, prm, split)
+                              : rk_launch_geo<T, NKT, S, 0, true, false, true>(stream, prm, split);
   if (prm.ids != nullptr) return rk_launch_geo<T, NKT, S, 0, true, true>(stream, prm, split);
   // (GEO 1 — 64-byte rows through a 4-stage ring, three chunks in flight instead of one — measured
   // slower: 95.9 vs 89.7 ms per config-5 step, twice the barriers for no gain in the gather rate;
@@ -1278,16 +1360,16 @@ int rk_launch(void* stream, const RkParams& prm) {
 // the counting and pair forms (MODE kCount / kPair): unsplit, GEO 0, the chunk count and K
 // compile-time by rk_launch_geo's rule (d = 768, and K = 64, in 16-bit) — a pair's score has the
 // bits of the ranking form that the same shape launches
-template <class T, int NKT, int S, int MODE>
+template <class T, int NKT, int S, int MODE, bool BIAS>
 int rk_launch_form(void* stream, const RkParams& prm) {
   constexpr bool P = MODE == kPair;              // the pair form gathers: SUB (and so FLT)
-  void (*kern)(RkParams) = rk_fused<T, NKT, S, 0, 1, 0, 0, P, P, MODE>;
+  void (*kern)(RkParams) = rk_fused<T, NKT, S, 0, 1, 0, 0, P, P, MODE, BIAS>;
   if constexpr (sizeof(T) == 2) {
     constexpr int kN768 = 768 * 2 / kRB<0>;
     if (prm.d == 768) {
-      kern = rk_fused<T, NKT, S, kN768, 1, 0, 0, P, P, MODE>;
+      kern = rk_fused<T, NKT, S, kN768, 1, 0, 0, P, P, MODE, BIAS>;
       if constexpr (NKT == 2)
-        if (prm.K == 64) kern = rk_fused<T, NKT, S, kN768, 1, 0, 64, P, P, MODE>;
+        if (prm.K == 64) kern = rk_fused<T, NKT, S, kN768, 1, 0, 64, P, P, MODE, BIAS>;
     }
   }
   constexpr int NR = S == MINER_SCORE_WEIGHTED ? 2 * NKT : NKT;
@@ -1301,24 +1383,38 @@ int rk_launch_form(void* stream, const RkParams& prm) {
   return e == hipSuccess ? MINER_OK : (int)e;
 }
 
-template <class T, int MODE>
+template <class T, int MODE, bool BIAS>
 int rk_dispatch_form(void* stream, const RkParams& prm) {
   const int st = prm.score_type;
   if (prm.K <= 32) {
-    if (st == MINER_SCORE_WEIGHTED) return rk_launch_form<T, 1, MINER_SCORE_WEIGHTED, MODE>(stream, prm);
-    if (st == MINER_SCORE_MAX) return rk_launch_form<T, 1, MINER_SCORE_MAX, MODE>(stream, prm);
-    return rk_launch_form<T, 1, MINER_SCORE_MEAN, MODE>(stream, prm);
+    if (st == MINER_SCORE_WEIGHTED) return rk_launch_form<T, 1, MINER_SCORE_WEIGHTED, MODE, BIAS>(stream, prm);
+    if (st == MINER_SCORE_MAX) return rk_launch_form<T, 1, MINER_SCORE_MAX, MODE, BIAS>(stream, prm);
+    return rk_launch_form<T, 1, MINER_SCORE_MEAN, MODE, BIAS>(stream, prm);
   }
-  if (st == MINER_SCORE_WEIGHTED) return rk_launch_form<T, 2, MINER_SCORE_WEIGHTED, MODE>(stream, prm);
-  if (st == MINER_SCORE_MAX) return rk_launch_form<T, 2, MINER_SCORE_MAX, MODE>(stream, prm);
-  return rk_launch_form<T, 2, MINER_SCORE_MEAN, MODE>(stream, prm);
+  if (st == MINER_SCORE_WEIGHTED) return rk_launch_form<T, 2, MINER_SCORE_WEIGHTED, MODE, BIAS>(stream, prm);
+  if (st == MINER_SCORE_MAX) return rk_launch_form<T, 2, MINER_SCORE_MAX, MODE, BIAS>(stream, prm);
+  return rk_launch_form<T, 2, MINER_SCORE_MEAN, MODE, BIAS>(stream, prm);
 }
 
+// (the biased instantiation only when a prior table was given: the unbiased calls launch what they did)
+template <int MODE, bool BIAS>
+int rk_run_form_b(void* stream, int dtype, const RkParams& prm) {
+  if (dtype == MINER_DTYPE_BF16) return rk_dispatch_form<__bf16, MODE, BIAS>(stream, prm);
+  if (dtype == MINER_DTYPE_F16) return rk_dispatch_form<_Float16, MODE, BIAS>(stream, prm);
+  return rk_dispatch_form<float, MODE, BIAS>(stream, prm);
+}
 template <int MODE>
 int rk_run_form(void* stream, int dtype, const RkParams& prm) {
-  if (dtype == MINER_DTYPE_BF16) return rk_dispatch_form<__bf16, MODE>(stream, prm);
-  if (dtype == MINER_DTYPE_F16) return rk_dispatch_form<_Float16, MODE>(stream, prm);
-  return rk_dispatch_form<float, MODE>(stream, prm);
+  return prm.bias != nullptr ? rk_run_form_b<MODE, true>(stream, dtype, prm) : rk_run_form_b<MODE, false>(stream, dtype, prm);
+}
+
+// the prior table's checks, shared by the three biased entry points (after each one's own)
+int bias_check(const float* news_bias, int G, const int32_t* user_group) {
+  if (news_bias != nullptr && G <= 0) return MINER_EINVAL;
+  if (news_bias == nullptr && user_group != nullptr) return MINER_EINVAL;
+  if (!aligned4(news_bias)) return MINER_EALIGN;
+  if (!aligned4(user_group)) return MINER_EALIGN;
+  return MINER_OK;
 }
 
 template <class T>
@@ -1345,7 +1441,8 @@ int check_dims(int dtype, int d, int Dc, int K) {
 // table forms' checks, which keep their order and codes)
 int rk_run(void* stream, int dtype, int score_type, const void* user_mui, const void* user_proj, const void* news, int U,
            int N, int d, int K, int topk, const int32_t* exclude_ids, int E, const uint32_t* news_ok, bool subset,
-           const int32_t* news_ids, int M, float* top_scores, int32_t* top_ids, void* workspace, size_t workspace_bytes) {
+           const int32_t* news_ids, int M, float* top_scores, int32_t* top_ids, void* workspace, size_t workspace_bytes,
+           const float* news_bias = nullptr, int G = 0, const int32_t* user_group = nullptr) {
   const int ck = check_dims(dtype, d, 1, K);
   if (ck != MINER_OK) return ck;
   if (score_type < MINER_SCORE_WEIGHTED || score_type > MINER_SCORE_MEAN) return MINER_EINVAL;
@@ -1361,6 +1458,8 @@ int rk_run(void* stream, int dtype, int score_type, const void* user_mui, const 
     if (M < 0 || (M > 0 && !news_ids)) return MINER_EINVAL;
     if (!aligned4(news_ids)) return MINER_EALIGN;
   }
+  const int bk = bias_check(news_bias, G, user_group);
+  if (bk != MINER_OK) return bk;
   if (U == 0) return MINER_OK;
   RkParams prm{};
   if (!aligned16(workspace)) return MINER_EALIGN;
@@ -1380,6 +1479,7 @@ int rk_run(void* stream, int dtype, int score_type, const void* user_mui, const 
   prm.U = U; prm.N = N; prm.d = d; prm.K = K; prm.topk = topk; prm.score_type = score_type;
   prm.excl = E > 0 ? exclude_ids : nullptr; prm.E = E; prm.ok = news_ok;
   prm.ids = subset ? news_ids : nullptr; prm.M = subset ? M : 0;
+  prm.bias = news_bias; prm.grp = news_bias ? user_group : nullptr; prm.G = news_bias ? G : 0;
   if (dtype == MINER_DTYPE_BF16) return rk_dispatch<__bf16>(stream, prm);
   if (dtype == MINER_DTYPE_F16) return rk_dispatch<_Float16>(stream, prm);
   return rk_dispatch<float>(stream, prm);
@@ -1405,31 +1505,52 @@ extern "C" {
 
 int miner_score_pairs(void* stream, int dtype, int score_type, const void* user_mui, const void* user_proj,
                       const void* news, int U, int N, int d, int K, const int32_t* cand_ids, int C, float* scores) {
+  return miner_score_pairs_biased(stream, dtype, score_type, user_mui, user_proj, news, U, N, d, K, cand_ids, C, scores,
+                                  nullptr, 0, nullptr);
+}
+
+int miner_score_pairs_biased(void* stream, int dtype, int score_type, const void* user_mui, const void* user_proj,
+                             const void* news, int U, int N, int d, int K, const int32_t* cand_ids, int C, float* scores,
+                             const float* news_bias, int G, const int32_t* user_group) {
   const int ck = rk_check_common(dtype, score_type, user_mui, user_proj, news, U, N, d, K);
   if (ck != MINER_OK) return ck;
   if (C < 0 || (C > 0 && (!cand_ids || !scores))) return MINER_EINVAL;
   if (!aligned4(cand_ids) || !aligned4(scores)) return MINER_EALIGN;
+  const int bk = bias_check(news_bias, G, user_group);
+  if (bk != MINER_OK) return bk;
   if (U == 0 || C == 0) return MINER_OK;
   RkParams prm{};
   prm.mui = user_mui; prm.proj = user_proj; prm.news = news; prm.top_s = scores;
   prm.U = U; prm.N = N; prm.d = d; prm.K = K; prm.score_type = score_type;
   prm.ids = cand_ids; prm.M = C;
+  prm.bias = news_bias; prm.grp = news_bias ? user_group : nullptr; prm.G = news_bias ? G : 0;
   return rk_run_form<kPair>(stream, dtype, prm);
 }
 
 int miner_rank_count(void* stream, int dtype, int score_type, const void* user_mui, const void* user_proj,
                      const void* news, int U, int N, int d, int K, const float* target_scores, const int32_t* target_ids,
                      int T, const uint32_t* news_ok, int32_t* counts) {
+  return miner_rank_count_biased(stream, dtype, score_type, user_mui, user_proj, news, U, N, d, K, target_scores, target_ids,
+                                 T, news_ok, counts, nullptr, 0, nullptr);
+}
+
+int miner_rank_count_biased(void* stream, int dtype, int score_type, const void* user_mui, const void* user_proj,
+                            const void* news, int U, int N, int d, int K, const float* target_scores,
+                            const int32_t* target_ids, int T, const uint32_t* news_ok, int32_t* counts,
+                            const float* news_bias, int G, const int32_t* user_group) {
   const int ck = rk_check_common(dtype, score_type, user_mui, user_proj, news, U, N, d, K);
   if (ck != MINER_OK) return ck;
   if (T <= 0 || !target_scores || !target_ids || !counts) return MINER_EINVAL;
   if (T > kMaxT) return MINER_ESHAPE;
   if (!aligned4(target_scores) || !aligned4(target_ids) || !aligned4(news_ok) || !aligned4(counts)) return MINER_EALIGN;
+  const int bk = bias_check(news_bias, G, user_group);
+  if (bk != MINER_OK) return bk;
   if (U == 0) return MINER_OK;
   RkParams prm{};
   prm.mui = user_mui; prm.proj = user_proj; prm.news = news; prm.top_i = counts;
   prm.U = U; prm.N = N; prm.d = d; prm.K = K; prm.score_type = score_type;
   prm.ok = news_ok; prm.tgt_s = target_scores; prm.tgt_i = target_ids; prm.T = T;
+  prm.bias = news_bias; prm.grp = news_bias ? user_group : nullptr; prm.G = news_bias ? G : 0;
   return rk_run_form<kCount>(stream, dtype, prm);
 }
 
@@ -1518,6 +1639,17 @@ int miner_rank_topk_subset(void* stream, int dtype, int score_type, const void* 
                            void* workspace, size_t workspace_bytes) {
   return rk_run(stream, dtype, score_type, user_mui, user_proj, news, U, N, d, K, topk, exclude_ids, E, news_ok, true,
                 news_ids, M, top_scores, top_ids, workspace, workspace_bytes);
+}
+
+int miner_rank_topk_biased(void* stream, int dtype, int score_type, const void* user_mui, const void* user_proj,
+                           const void* news, int U, int N, int d, int K, int topk, const int32_t* exclude_ids, int E,
+                           const uint32_t* news_ok, const int32_t* news_ids, int M, float* top_scores, int32_t* top_ids,
+                           void* workspace, size_t workspace_bytes, const float* news_bias, int G,
+                           const int32_t* user_group) {
+  const bool table = news_ids == nullptr && M < 0;     // the whole table: the filtered form
+  return rk_run(stream, dtype, score_type, user_mui, user_proj, news, U, N, d, K, topk, exclude_ids, E, news_ok, !table,
+                table ? nullptr : news_ids, table ? 0 : M, top_scores, top_ids, workspace, workspace_bytes, news_bias, G,
+                user_group);
 }
 
 int miner_topk_merge(void* stream, const float* a_scores, const int32_t* a_ids, int ka, const float* b_scores,
