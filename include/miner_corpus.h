@@ -25,6 +25,9 @@
  *   miner_rank_topk_biased(...), miner_score_pairs_biased(...), miner_rank_count_biased(...)
  *                             the ranking, pair and counting forms with a per-news fp32 prior added
  *                             to the click score before it is used.
+ *   miner_rank_topk_capped(...), miner_topk_merge_capped(...)
+ *                             the ranking and list-merge forms with at most `cap` news of one
+ *                             cluster (story, publisher) per list.
  *
  * Conventions are those of miner_score.h. dtype: MINER_DTYPE_F32 (exact fp32, parity mode),
  * MINER_DTYPE_BF16 or MINER_DTYPE_F16 (16-bit operands, fp32 accumulation and softmax).
@@ -241,6 +244,52 @@ int miner_rank_count_biased(void* stream, int dtype, int score_type, const void*
                             const float* target_scores, const int32_t* target_ids, int T,
                             const uint32_t* news_ok, int32_t* counts, const float* news_bias, int G,
                             const int32_t* user_group);
+
+/*
+ * Per-cluster caps: at most `cap` news of one cluster (a story, a publisher, a sub-category) in a
+ * user's list.
+ *   news_cluster [N] int32 device pointer, 4-byte aligned: news_cluster[n] >= 0 is the cluster of
+ *               news n (arbitrary non-negative values, need not be dense); < 0: in no cluster, never
+ *               capped.
+ *   cap         1 <= cap <= MINER_CORPUS_MAX_TOPK, one value for every cluster and user.
+ * User u's capped list is a walk of its complete ranking — the one the uncapped call would give with
+ * topk = N under the same exclude_ids, news_ok, news_ids and news_bias, score descending, then lower
+ * news id: an entry is kept iff fewer than cap entries of its cluster were kept before it (an
+ * unclustered entry always); the walk stops after topk kept entries, and a shorter list ends in
+ * (-inf, -1). No score changes: a listed entry carries, bit for bit, the score the uncapped call
+ * gives that pair. An excluded or ineligible news does not use up its cluster's cap; a NaN score is
+ * never listed and does not count. Within a cluster the best cap survivors are kept, so capped lists
+ * merge as top-k lists do: capped(A u B) = capped(capped(A) u capped(B)) for disjoint A and B.
+ *
+ * miner_rank_topk_capped: miner_rank_topk_biased's arguments (news_ids NULL with M < 0: the whole
+ * table; news_bias / user_group present or NULL), then the two above. Every dtype, score type, K and
+ * d of the biased form. With news_cluster NULL it returns exactly what miner_rank_topk_biased returns
+ * on the other arguments (it launches the same kernel; cap is read only with a table, as G is).
+ * With a table the UNSPLIT form runs whatever the workspace: a workspace is accepted (checked as
+ * before) and never written — there is no split form under caps, so a small batch (U <= 510) does
+ * not get the split form's 8x workgroups.
+ *
+ * miner_topk_merge_capped: miner_topk_merge (b-over-a replacement, then the bitmap pruning), then the
+ * best topk of the capped walk over what is left. The input rows need not be sorted and need not be
+ * capped themselves (an uncapped list through this call with ka = 0 is its post-hoc cap: the first
+ * entries of the true capped list, and all of it wherever it fills topk or the input was not full).
+ *   news_cluster holds n_cluster entries; an entry whose id is at or past n_cluster is in no
+ *   cluster and no table word is read for it. With news_cluster NULL it is miner_topk_merge.
+ * After the base call's own checks, in their order and with their codes: a table with cap <= 0:
+ * MINER_EINVAL; cap > MINER_CORPUS_MAX_TOPK: MINER_ESHAPE; (merge form) a table with
+ * n_cluster <= 0: MINER_EINVAL; a misaligned news_cluster: MINER_EALIGN (all before any launch, and
+ * before the U == 0 return).
+ */
+int miner_rank_topk_capped(void* stream, int dtype, int score_type, const void* user_mui,
+                           const void* user_proj, const void* news, int U, int N, int d, int K, int topk,
+                           const int32_t* exclude_ids, int E, const uint32_t* news_ok,
+                           const int32_t* news_ids, int M, float* top_scores, int32_t* top_ids,
+                           void* workspace, size_t workspace_bytes, const float* news_bias, int G,
+                           const int32_t* user_group, const int32_t* news_cluster, int cap);
+int miner_topk_merge_capped(void* stream, const float* a_scores, const int32_t* a_ids, int ka,
+                            const float* b_scores, const int32_t* b_ids, int kb, int U, int topk,
+                            const uint32_t* news_ok, int N, float* out_scores, int32_t* out_ids,
+                            const int32_t* news_cluster, int n_cluster, int cap);
 
 #ifdef __cplusplus
 }

@@ -121,6 +121,7 @@ ASAN_DRIVER = os.path.join(ROOT, "tests", "native", "abi_errors.cpp")
 ASAN_DRIVER_SUBSET = os.path.join(ROOT, "tests", "native", "abi_errors_subset.cpp")
 ASAN_DRIVER_RANK = os.path.join(ROOT, "tests", "native", "abi_errors_rank.cpp")
 ASAN_DRIVER_BIAS = os.path.join(ROOT, "tests", "native", "abi_errors_bias.cpp")
+ASAN_DRIVER_CAP = os.path.join(ROOT, "tests", "native", "abi_errors_cap.cpp")
 
 
 def build_asan_driver(force: bool = False, verbose: bool = False, driver: str = ASAN_DRIVER) -> str:
@@ -185,11 +186,18 @@ def build_asan_driver_bias(force: bool = False, verbose: bool = False) -> str:
     return build_asan_driver(force=force, verbose=verbose, driver=ASAN_DRIVER_BIAS)
 
 
+def build_asan_driver_cap(force: bool = False, verbose: bool = False) -> str:
+    """build/asan/abi_errors_cap: the error paths of miner_rank_topk_capped and miner_topk_merge_capped
+    (tests/native/abi_errors_cap.cpp; run by tests/test_corpus_cap_host.py)."""
+    return build_asan_driver(force=force, verbose=verbose, driver=ASAN_DRIVER_CAP)
+
+
 if __name__ == "__main__":
     if "--asan" in sys.argv:
         print(build_asan_driver(force="--force" in sys.argv, verbose=True))
         print(build_asan_driver_subset(verbose=True))
         print(build_asan_driver_rank(verbose=True))
         print(build_asan_driver_bias(verbose=True))
+        print(build_asan_driver_cap(verbose=True))
     else:
         print(build_library(force="--force" in sys.argv, verbose=True, debug="--debug" in sys.argv))

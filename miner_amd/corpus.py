@@ -15,6 +15,10 @@ d=768, fp16), backed by libminer_hip.so (include/miner_corpus.h).
     rank_topk(..., news_bias=prior)                        # fp32 [N] or [G, N] (+ user_group [U]) added to the
                                                            # click score before it ranks; also score_pairs, rank_of,
                                                            # update_topk, rescore_topk, rank_corpus, evaluate_corpus
+    rank_topk(..., news_cluster=story, cluster_cap=1)      # at most cluster_cap news of one cluster (int [N], < 0:
+                                                           # none) per list, inside the ranker's merge; also merge_topk,
+                                                           # update_topk, rank_corpus; cap_topk(lists, story, 1) caps a
+                                                           # served list (unsplit kernel only; not rank_of / score_pairs)
 
 The click score of (user, news) is the reference's (src/model/model.py:127-134, 213-214) with the
 impression's candidate set replaced by the whole news table; ties rank the lower news id first.
@@ -216,10 +220,44 @@ def _prior(news_bias, user_group, U: int, N: int) -> Optional[_Prior]:
     return _Prior(news_bias.reshape(G, N).contiguous(), _contig(user_group, torch.int32))
 
 
+@dataclasses.dataclass
+class _Caps:
+    """Checked per-cluster caps: cluster int32 [N] contiguous on the device, cap in [1, MAX_TOPK]."""
+    cluster: Tensor
+    cap: int
+
+
+def _caps(news_cluster, cluster_cap, N: Optional[int]) -> Optional[_Caps]:
+    """news_cluster= / cluster_cap= of the ranking and merging entries -> a _Caps, or None without
+    caps. Everything but the value range is checked before anything touches the device. ``N``: the
+    length the table must have (None: any, at least one entry — the merging entries)."""
+    if isinstance(news_cluster, _Caps):
+        if cluster_cap is not None:
+            raise ValueError("cluster_cap is part of the checked caps")
+        if N is not None and news_cluster.cluster.shape[0] != N:
+            raise ValueError(f"the cluster table was made for {news_cluster.cluster.shape[0]} news, not {N}")
+        return news_cluster
+    if news_cluster is None and cluster_cap is None:
+        return None
+    if news_cluster is None or cluster_cap is None:
+        raise ValueError("news_cluster and cluster_cap go together")
+    if isinstance(cluster_cap, bool) or not isinstance(cluster_cap, int) or not 1 <= cluster_cap <= MAX_TOPK:
+        raise ValueError(f"cluster_cap must be an int in [1, {MAX_TOPK}]")
+    if not isinstance(news_cluster, Tensor) or news_cluster.dim() != 1 or news_cluster.is_floating_point() \
+            or news_cluster.is_complex() or news_cluster.dtype == torch.bool or news_cluster.shape[0] < 1 \
+            or (N is not None and news_cluster.shape[0] != N):
+        raise ValueError("news_cluster must be a 1-D integer tensor" + (f" of {N} entries" if N is not None else ""))
+    if news_cluster.dtype != torch.int32:
+        if int(news_cluster.min()) < -2 ** 31 or int(news_cluster.max()) > 2 ** 31 - 1:
+            raise ValueError("news_cluster values must fit int32")
+    _require_device(news_cluster)
+    return _Caps(_contig(news_cluster, torch.int32), cluster_cap)
+
+
 def rank_topk(user_mui: Tensor, user_proj: Optional[Tensor], news: Tensor, topk: int, *,
               score_type: str = "weighted", exclude_ids: Optional[Tensor] = None,
               eligible: Optional[Tensor] = None, news_ids=None, news_bias=None,
-              user_group: Optional[Tensor] = None):
+              user_group: Optional[Tensor] = None, news_cluster=None, cluster_cap: Optional[int] = None):
     """Top-k news per user by the click score, best first: (scores [U,topk] fp32, ids [U,topk]
     int32); entries past the table size are (-inf, -1).
 
@@ -243,8 +281,19 @@ def rank_topk(user_mui: Tensor, user_proj: Optional[Tensor], news: Tensor, topk:
     the score returned. Filters, ties (lower id first) and ``news_ids`` work on the table id as
     before. A prior is not a filter: a -inf prior still lists the news while a list has room (use
     ``eligible``); +inf ranks it first; a NaN sum is never listed. Without news_bias the call is
-    today's."""
+    today's.
+
+    news_cluster / cluster_cap: per-cluster caps. news_cluster is an integer [N] tensor (values must
+    fit int32): >= 0 the cluster of news n (a story, a publisher; arbitrary values), < 0 in no
+    cluster; cluster_cap an int in [1, 256]; one without the other is an error. The list is the walk
+    of the user's complete ranking (under every other argument, as with topk = N) that keeps an entry
+    iff fewer than cluster_cap entries of its cluster were kept before it, stopped after topk kept
+    entries ((-inf, -1) after a shorter one). Scores are the uncapped call's, bit for bit; an
+    excluded or ineligible news uses up no cap. The capped ranker has no split form: a batch of
+    U <= 510 users runs the unsplit kernel (MINER_RK_SPLIT is ignored), at the price
+    profiles/rk_cap_ab.txt records. With both None the call is today's."""
     pri = _prior(news_bias, user_group, user_mui.shape[0], news.shape[0])
+    caps = _caps(news_cluster, cluster_cap, news.shape[0])
     st = _lib.SCORE_TYPES.get(score_type)
     if st is None or st == _lib.SCORE_NONE:
         raise ValueError("Invalid method of aggregating matching score")  # model.py:136
@@ -282,10 +331,18 @@ def rank_topk(user_mui: Tensor, user_proj: Optional[Tensor], news: Tensor, topk:
     lib = _lib.lib()
     force = os.environ.get("MINER_RK_SPLIT", "")
     split = force == "1" if force in ("0", "1") else bool(lib.miner_rank_topk_split_recommended(U))
+    split = split and caps is None
     nws = int(lib.miner_rank_topk_workspace_bytes(U, topk)) if split else 0
     ws = torch.empty(nws, dtype=torch.uint8, device=dev) if nws else None
     with torch.cuda.device(dev):
-        if pri is not None:
+        if caps is not None:                                 # unsplit whatever the batch: no workspace
+            M = -1 if sub is None else sub.ids.numel()
+            rc = lib.miner_rank_topk_capped(_stream(dev), dt, st, _ptr(mui), _ptr(proj), _ptr(tab), U, N, d, K, topk,
+                                            _ptr(excl), E, _ptr(ok), _ptr(sub.ids) if M > 0 else None, M,
+                                            _ptr(top_s), _ptr(top_i), None, 0,
+                                            None if pri is None else _ptr(pri.bias), 0 if pri is None else pri.G,
+                                            None if pri is None else _ptr(pri.group), _ptr(caps.cluster), caps.cap)
+        elif pri is not None:
             M = -1 if sub is None else sub.ids.numel()       # -1 with no list: the whole table
             rc = lib.miner_rank_topk_biased(_stream(dev), dt, st, _ptr(mui), _ptr(proj), _ptr(tab), U, N, d, K, topk,
                                             _ptr(excl), E, _ptr(ok), _ptr(sub.ids) if M > 0 else None, M,
@@ -318,14 +375,20 @@ def _list_pair(lists, what: str):
     return _contig(s, torch.float32), _contig(i, torch.int32)
 
 
-def merge_topk(a, b, topk: Optional[int] = None, *, eligible: Optional[Tensor] = None):
+def merge_topk(a, b, topk: Optional[int] = None, *, eligible: Optional[Tensor] = None, news_cluster=None,
+               cluster_cap: Optional[int] = None):
     """Merge two per-user top-k lists (scores [U,k] fp32, ids [U,k] integer; k <= 256 each) on the
     device under the ranker's order (score descending, then lower news id): the best ``topk``
     (default: the wider list's k) of their union, then the (-inf, -1) tail. A news in both lists
     keeps b's entry — a fresh score replaces a stale one — and entries with id < 0 hold nothing; the
     rows need not be sorted. ``eligible`` (bool [N] or pack_eligible's int32 words; a bool mask gives
     N, packed words cover 32 · len news) drops the entries of news that are no longer eligible.
-    For disjoint id sets A and B, merge_topk(rank(A), rank(B)) is rank(A ∪ B), bit for bit."""
+    For disjoint id sets A and B, merge_topk(rank(A), rank(B)) is rank(A ∪ B), bit for bit.
+    ``news_cluster`` / ``cluster_cap`` (as in rank_topk; the table may be any length >= 1, an id at or
+    past it is in no cluster): after the replacement and the pruning, the capped walk over what is
+    left — the inputs need not be capped. Capped lists merge as top-k lists do: for disjoint A and
+    B, merge_topk(capped(A), capped(B), caps) is capped(A ∪ B), bit for bit."""
+    caps = _caps(news_cluster, cluster_cap, None)
     a_s, a_i = _list_pair(a, "list a")
     b_s, b_i = _list_pair(b, "list b")
     U, ka = a_s.shape
@@ -350,32 +413,63 @@ def merge_topk(a, b, topk: Optional[int] = None, *, eligible: Optional[Tensor] =
     out_s = torch.empty(U, topk, dtype=torch.float32, device=dev)
     out_i = torch.empty(U, topk, dtype=torch.int32, device=dev)
     with torch.cuda.device(dev):
-        rc = _lib.lib().miner_topk_merge(_stream(dev), _ptr(a_s) if ka else None, _ptr(a_i) if ka else None, ka,
-                                         _ptr(b_s) if kb else None, _ptr(b_i) if kb else None, kb, U, topk, _ptr(ok), N,
-                                         _ptr(out_s), _ptr(out_i))
+        if caps is not None:
+            rc = _lib.lib().miner_topk_merge_capped(_stream(dev), _ptr(a_s) if ka else None, _ptr(a_i) if ka else None,
+                                                    ka, _ptr(b_s) if kb else None, _ptr(b_i) if kb else None, kb, U,
+                                                    topk, _ptr(ok), N, _ptr(out_s), _ptr(out_i), _ptr(caps.cluster),
+                                                    caps.cluster.shape[0], caps.cap)
+        else:
+            rc = _lib.lib().miner_topk_merge(_stream(dev), _ptr(a_s) if ka else None, _ptr(a_i) if ka else None, ka,
+                                             _ptr(b_s) if kb else None, _ptr(b_i) if kb else None, kb, U, topk, _ptr(ok),
+                                             N, _ptr(out_s), _ptr(out_i))
     _lib.check(rc, "miner_topk_merge")
     return out_s, out_i
 
 
 def update_topk(lists, user_mui: Tensor, user_proj: Optional[Tensor], news: Tensor, news_ids, *,
                 score_type: str = "weighted", exclude_ids: Optional[Tensor] = None,
-                eligible: Optional[Tensor] = None, news_bias=None, user_group: Optional[Tensor] = None):
+                eligible: Optional[Tensor] = None, news_bias=None, user_group: Optional[Tensor] = None,
+                news_cluster=None, cluster_cap: Optional[int] = None):
     """Incremental ranking: ``lists`` = (scores [U,k], ids [U,k]) ranked earlier for these users; the
     table rows ``news_ids`` (new or changed news) are ranked with rank_topk(news_ids=...) and merged
     in with merge_topk — a re-ranked news takes its fresh score. ``exclude_ids`` filters the fresh
     rows as in rank_topk; ``eligible`` filters them and also prunes expired news from ``lists``.
     Returns the new (scores [U,k], ids [U,k]); the cost follows len(news_ids), not the table.
     ``news_bias`` / ``user_group`` as in rank_topk: the fresh rows are ranked under the prior that
-    ``lists`` was ranked under (a list ranked under another prior holds stale scores: rescore_topk)."""
+    ``lists`` was ranked under (a list ranked under another prior holds stale scores: rescore_topk).
+    ``news_cluster`` / ``cluster_cap`` as in rank_topk: the fresh rows are ranked under the caps and
+    merged with the capped merge. Exact: where the fresh ids are new to ``lists`` (disjoint id sets)
+    and ``lists`` is the capped ranking of the old ids under the same table, the result is the
+    capped ranking of the union, bit for bit. Stale, as a list under another prior is: a capped
+    list holds only what its caps let through, so when ``eligible`` prunes an entry, or a re-ranked
+    news comes back with a lower score, the same-cluster news that entry once displaced is no longer
+    in the list and does not return — the result is within its caps, but may miss that news until
+    the users are ranked again."""
     pri = _prior(news_bias, user_group, user_mui.shape[0], news.shape[0])
+    caps = _caps(news_cluster, cluster_cap, news.shape[0])
     old = _list_pair(lists, "lists")
     k = old[0].shape[1]
     if k < 1:
         raise ValueError("lists must hold at least one entry per user")
     ok = None if eligible is None else _eligible_words(eligible, news.shape[0])
     fresh = rank_topk(user_mui, user_proj, news, k, score_type=score_type, exclude_ids=exclude_ids, eligible=ok,
-                      news_ids=news_ids, news_bias=pri)
-    return merge_topk(old, fresh, k, eligible=ok)
+                      news_ids=news_ids, news_bias=pri, news_cluster=caps)
+    return merge_topk(old, fresh, k, eligible=ok, news_cluster=caps)
+
+
+def cap_topk(lists, news_cluster, cluster_cap: int, topk: Optional[int] = None):
+    """The post-hoc cap of served lists (scores [U,k], ids [U,k]; k <= 256, rows in any order): the
+    capped walk of each row (rank_topk's ``news_cluster`` / ``cluster_cap``), the best ``topk``
+    (default k) kept entries, then (-inf, -1) — the capped merge with an empty first list. The cap of
+    a list is prefix-exact: capping an uncapped top-k gives the first entries of the true capped
+    list, so the result IS rank_topk's capped list wherever it fills ``topk`` or the input list was
+    not full (then the input held every admissible news); a row that comes back short from a full
+    input needs the capped ranker."""
+    caps = _caps(news_cluster, cluster_cap, None)
+    s, i = _list_pair(lists, "lists")
+    if s.shape[1] < 1:
+        raise ValueError("lists must hold at least one entry per user")
+    return merge_topk((s[:, :0], i[:, :0]), (s, i), s.shape[1] if topk is None else topk, news_cluster=caps)
 
 
 MAX_TARGETS = 64
@@ -639,7 +733,7 @@ def rank_corpus(news: Tensor, his_ids: Tensor, his_mask: Tensor, packed: Encoder
                 his_bias: Optional[Tensor] = None, score_type: str = "weighted", batch: int = 16384,
                 out: Optional[tuple] = None, exclude_history: bool = False, exclude_ids: Optional[Tensor] = None,
                 eligible: Optional[Tensor] = None, news_ids=None, news_bias=None,
-                user_group: Optional[Tensor] = None):
+                user_group: Optional[Tensor] = None, news_cluster=None, cluster_cap: Optional[int] = None):
     """BASELINE config 5 on one GPU's share of the users: every user (his_ids [U,L] into the news
     table [N,d], his_mask [U,L]) encoded and ranked against the whole table, ``batch`` users per
     encode + rank pair so that the [batch,K,d] user vectors are all that is ever held (125,000 users
@@ -649,12 +743,14 @@ def rank_corpus(news: Tensor, his_ids: Tensor, his_mask: Tensor, packed: Encoder
 
     ``exclude_history`` keeps each user's own clicked news (the unmasked his_ids) out of its list,
     ``exclude_ids`` [U,E] further ids, together at most 256 per user; ``eligible`` and ``news_ids`` (rank only these table rows) as in
-    rank_topk; ``news_bias`` / ``user_group`` [U] (a score prior, checked once and sliced per batch) too."""
+    rank_topk; ``news_bias`` / ``user_group`` [U] (a score prior, checked once and sliced per batch) too;
+    ``news_cluster`` / ``cluster_cap`` (per-cluster caps, checked and converted once) too."""
     if batch <= 0:
         raise ValueError("batch must be positive")
     U = his_ids.shape[0]
     dev = news.device
     pri = _prior(news_bias, user_group, U, news.shape[0])
+    caps = _caps(news_cluster, cluster_cap, news.shape[0])
     _require_device(news, his_ids, his_mask, exclude_ids, eligible)
     excl = exclude_ids
     if excl is not None and (excl.dim() != 2 or excl.shape[0] != U):
@@ -675,7 +771,7 @@ def rank_corpus(news: Tensor, his_ids: Tensor, his_mask: Tensor, packed: Encoder
                                  his_bias=None if his_bias is None else his_bias[u0:u1], with_proj=with_proj)
         s, i = rank_topk(mui, proj, news, topk, score_type=score_type,
                          exclude_ids=None if excl is None else excl[u0:u1], eligible=ok, news_ids=sub,
-                         news_bias=None if pri is None else pri.users(u0, u1))
+                         news_bias=None if pri is None else pri.users(u0, u1), news_cluster=caps)
         top_s[u0:u1] = s
         top_i[u0:u1] = i
     return top_s, top_i

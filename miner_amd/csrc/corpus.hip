@@ -461,6 +461,8 @@ struct RkParams {
   const float* bias;       // BIAS: the score priors [G][N] fp32, added to every score before it is used
   const int32_t* grp;      //       [U] prior rows (NULL: row 0 for every user), clamped into [0, G)
   int G;
+  const int32_t* clus;     // CAP: the cluster table [N] (< 0: in no cluster); a list holds at most cap news
+  int cap;                 //      of one cluster
 };
 
 // S > 1 (S = 8, grid = 256): the news steps are dealt to S slices (step st of slice s is news step
@@ -534,7 +536,7 @@ __device__ __forceinline__ unsigned rk_okey(float s) {
 }
 __device__ __forceinline__ unsigned rk_ikey(int id) { return (unsigned)id ^ 0x7fffffffu; }
 
-template <int NR, int GEO = 0, bool FLT = false>
+template <int NR, int GEO = 0, bool FLT = false, bool CAP = false>
 struct RkLds {
   static constexpr int kARows = kUT * NR * 32;
   static constexpr int kStage = (kARows + kNT) * kRB<GEO>;
@@ -542,7 +544,10 @@ struct RkLds {
   static constexpr int kOffStage = kOffList + kUT * kMaxTopk * 8;  // staged candidates [2 bufs][kUT][kNT]
   static constexpr int kOffCnt = kOffStage + 2 * kUT * kNT * 8;     // list counts [kUT], staged [2][kUT]
   static constexpr int kOffExcl = kOffCnt + 64;                     // the tile's exclusion lists [kUT][kMaxL] int
-  static constexpr int kTotal = kOffExcl + (FLT ? kUT * kMaxL * 4 : 0);
+  // CAP: per list entry its cluster id and its rank inside its cluster, [kUT][kMaxTopk] int each,
+  // then the cluster ids of the staged entries being merged [kUT][kNT]
+  static constexpr int kOffClus = kOffExcl + (FLT ? kUT * kMaxL * 4 : 0);
+  static constexpr int kTotal = kOffClus + (CAP ? (2 * kUT * kMaxTopk + kUT * kNT) * 4 : 0);
 };
 
 // NCH: RB-byte d-chunks per row (0: at run time); GEO: the stream geometry (kRB / kRing); FLT: the
@@ -569,6 +574,13 @@ struct RkLds {
 // (rk_add_rn) on the finished score — before the threshold test, the key compare or the store, so
 // lists, counts and pair scores agree bit for bit with "scores + prior" in fp32. A compile-time
 // switch for the reason FLT is one: the unbiased instantiations are the same code as without it.
+// CAP: the capped form (RkParams clus / cap; kRank, unsplit, GEO 0, filtered). A user's list is the
+// greedy walk of its ranking that keeps an entry iff fewer than cap better entries of its cluster
+// were kept — a mergeable summary as the top-k is, so only the merge changes (below): the contraction,
+// the epilogue, the threshold test and the staging are the uncapped form's, and a listed score has
+// its bits. To keep the build small the CAP instantiations are the BIAS ones with the prior tested at
+// run time (no table: nothing is loaded and nothing is added, so an unbiased capped score is not
+// "score + 0"); CAP is a compile-time switch so that every other instantiation is the code it was.
 constexpr int kRank = 0, kCount = 1, kPair = 2;
 constexpr int kMaxT = MINER_CORPUS_MAX_TARGETS;
 
@@ -580,8 +592,9 @@ __device__ __forceinline__ float rk_add_rn(float a, float b) {
 }
 
 template <class T, int NKT, int SCORE, int NCH = 0, int S = 1, int GEO = 0, int KC = 0, bool FLT = false,   // KC: K compile-time (0: run time)
-          bool SUB = false, int MODE = kRank, bool BIAS = false>
+          bool SUB = false, int MODE = kRank, bool BIAS = false, bool CAP = false>
 __global__ __launch_bounds__(kThreads) void rk_fused(RkParams p) {
+  static_assert(!CAP || (MODE == kRank && S == 1 && GEO == 0 && FLT && BIAS), "the capped form: unsplit, filtered, on the biased form");
   static_assert(!SUB || (FLT && GEO == 0), "the subset form: a filtered form with one chunk in flight");
   static_assert(!BIAS || (GEO == 0 && (FLT || MODE == kCount)), "the biased forms: GEO 0, the ranking forms filtered");
   static_assert(MODE == kRank || (S == 1 && GEO == 0 && SUB == (MODE == kPair)), "counting and pair forms: unsplit, GEO 0");
@@ -591,7 +604,7 @@ __global__ __launch_bounds__(kThreads) void rk_fused(RkParams p) {
   constexpr bool kW = SCORE == MINER_SCORE_WEIGHTED;
   constexpr int NR = kW ? 2 * NKT : NKT;            // row tiles per user: mui (and proj)
   constexpr int RB = kRB<GEO>, RING = kRing<GEO>, PD = RING - 1;   // PD: chunks in flight
-  using LD = RkLds<NR, GEO, FLT>;
+  using LD = RkLds<NR, GEO, FLT, CAP>;
   constexpr int kChunkSlabs = RB / (32 * (int)sizeof(T));          // 32-index slabs per chunk
   static_assert(kChunkSlabs >= 1, "a chunk holds whole slabs");
   const int d = NCH > 0 ? NCH * RB / (int)sizeof(T) : p.d, K = KC > 0 ? KC : p.K, N = p.N;
@@ -607,6 +620,9 @@ __global__ __launch_bounds__(kThreads) void rk_fused(RkParams p) {
   int* stg_i = reinterpret_cast<int*>(smem + LD::kOffStage + 2 * kUT * kNT * 4);
   int* cnt = reinterpret_cast<int*>(smem + LD::kOffCnt);   // [0, kUT) list sizes, kUT + buf * kUT + uu staged
   int* excl = reinterpret_cast<int*>(smem + LD::kOffExcl);  // [kUT][kMaxL], -1 past E (FLT and p.E > 0 only)
+  [[maybe_unused]] int* list_g = reinterpret_cast<int*>(smem + LD::kOffClus);                   // CAP: [kUT][kMaxTopk]
+  [[maybe_unused]] int* list_r = reinterpret_cast<int*>(smem + LD::kOffClus + kUT * kMaxTopk * 4);
+  [[maybe_unused]] int* stg_g = reinterpret_cast<int*>(smem + LD::kOffClus + 2 * kUT * kMaxTopk * 4);   // [kUT][kNT]
   // counting form (no list, nothing staged): the targets [kUT][kMaxT] and the waves' partial counts [kWaves][kMaxT]
   [[maybe_unused]] unsigned* tg_h = reinterpret_cast<unsigned*>(smem + LD::kOffList);   // key halves: score, id
   [[maybe_unused]] unsigned* tg_l = reinterpret_cast<unsigned*>(smem + LD::kOffList + kUT * kMaxT * 4);
@@ -735,6 +751,122 @@ __global__ __launch_bounds__(kThreads) void rk_fused(RkParams p) {
     constexpr int kLT = kMaxTopk / 64, kST = kNT / 64;
     float lv[kLT], sv[kST];
     int lid[kLT], sid[kST], lr[kLT], sr[kST];
+    if constexpr (CAP) {
+      // The capped merge: the capped list of (list ∪ staged). The list is a valid capped list, so
+      // each entry carries its cluster id and its rank inside its cluster (list_g / list_r).
+      // Pass 1: per entry of both sets, rc = the better entries of its own cluster in the union (a
+      // list entry: its carried rank plus the better staged ones); kept iff unclustered or rc < cap
+      // — the better entries of a kept entry's cluster are then kept too, so rc is also its rank
+      // among the kept and is carried on. Pass 2: an entry's position = the better KEPT entries (the
+      // list's: a prefix count of its kept mask). Every read of the list and of the staging buffer
+      // comes before the first write to the list.
+      // The staged entries' cluster ids are loaded HERE, by the one merging wave, first of all: the
+      // merge runs at a step's first chunk between the chunk's wait and the next chunk's DMA issue,
+      // so nothing else of this wave is in flight and the wait below is for these loads alone (the
+      // tile's last merge waits for the next tile's first chunk once). A load in the epilogue, by
+      // the staging lanes, would be waited with vmcnt(0) behind the next chunk's row DMAs on every
+      // wave that staged something.
+      int* lg_ = list_g + uu * kMaxTopk;
+      int* lrk_ = list_r + uu * kMaxTopk;
+      int* mg = stg_g + uu * kNT;
+      int sg[kST], lg[kLT], lrc[kLT], src[kST];
+#pragma unroll
+      for (int v = 0; v < kST; ++v) {
+        const int j = min(lane + 64 * v, kNT - 1);
+        sv[v] = ss[j];
+        sid[v] = si[j];
+        sg[v] = lane + 64 * v < ns ? p.clus[sid[v]] : -1;   // a staged id is a table row: inside [0, N)
+        src[v] = 0;
+      }
+#pragma unroll
+      for (int t = 0; t < kLT; ++t) {
+        const int i = min(lane + 64 * t, kMaxTopk - 1);
+        const bool in = lane + 64 * t < c;
+        lv[t] = ls[i];
+        lid[t] = li[i];
+        lg[t] = in ? lg_[i] : -1;
+        lrc[t] = lrk_[i];
+      }
+#pragma unroll
+      for (int v = 0; v < kST; ++v) mg[lane + 64 * v] = sg[v];
+      for (int j2 = 0; j2 < ns; ++j2) {
+        const int g2 = __builtin_amdgcn_readfirstlane(mg[j2]);
+        if (g2 < 0) continue;                    // never capped, and in nobody's cluster
+        const float s2 = ss[j2];
+        const int i2 = si[j2];
+        int nl = 0;                              // better list entries of cluster g2
+#pragma unroll
+        for (int t = 0; t < kLT; ++t) {
+          const bool same = lg[t] == g2;
+          lrc[t] += same && better(s2, i2, lv[t], lid[t]) ? 1 : 0;
+          nl += __popcll(__ballot(same && better(lv[t], lid[t], s2, i2)));
+        }
+#pragma unroll
+        for (int v = 0; v < kST; ++v) {
+          src[v] += sg[v] == g2 && better(s2, i2, sv[v], sid[v]) ? 1 : 0;
+          if (j2 == lane + 64 * v) src[v] += nl;
+        }
+      }
+      bool lk[kLT], sk[kST];
+      unsigned long long lkm[kLT], skm[kST];
+      int kept = 0;
+#pragma unroll
+      for (int t = 0; t < kLT; ++t) {
+        lk[t] = lane + 64 * t < c && (lg[t] < 0 || lrc[t] < p.cap);
+        lkm[t] = __ballot(lk[t]);
+        lr[t] = kept + __popcll(lkm[t] & ((1ull << lane) - 1));   // the better kept list entries
+        kept += __popcll(lkm[t]);
+      }
+#pragma unroll
+      for (int v = 0; v < kST; ++v) {
+        sk[v] = lane + 64 * v < ns && (sg[v] < 0 || src[v] < p.cap);
+        skm[v] = __ballot(sk[v]);
+        kept += __popcll(skm[v]);
+        sr[v] = 0;
+      }
+      for (int j2 = 0; j2 < ns; ++j2) {
+        const unsigned long long m = j2 < 64 ? skm[0] : j2 < 128 ? skm[1] : j2 < 192 ? skm[2] : skm[3];
+        static_assert(kST == 4, "four staged masks");
+        if (!((m >> (j2 & 63)) & 1)) continue;   // wave-uniform: a dropped entry displaces nothing
+        const float s2 = ss[j2];
+        const int i2 = si[j2];
+        int nl = 0;
+#pragma unroll
+        for (int t = 0; t < kLT; ++t) {
+          lr[t] += better(s2, i2, lv[t], lid[t]) ? 1 : 0;
+          nl += __popcll(__ballot(lk[t] && better(lv[t], lid[t], s2, i2)));
+        }
+#pragma unroll
+        for (int v = 0; v < kST; ++v) {
+          sr[v] += better(s2, i2, sv[v], sid[v]) ? 1 : 0;
+          if (j2 == lane + 64 * v) sr[v] += nl;
+        }
+      }
+      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+#pragma unroll
+      for (int t = 0; t < kLT; ++t) {
+        if (lk[t] && lr[t] < p.topk) {
+          ls[lr[t]] = lv[t];
+          li[lr[t]] = lid[t];
+          lg_[lr[t]] = lg[t];
+          lrk_[lr[t]] = lrc[t];
+        }
+      }
+#pragma unroll
+      for (int v = 0; v < kST; ++v) {
+        if (sk[v] && sr[v] < p.topk) {
+          ls[sr[v]] = sv[v];
+          li[sr[v]] = sid[v];
+          lg_[sr[v]] = sg[v];
+          lrk_[sr[v]] = src[v];
+        }
+      }
+      if (lane == 0) {
+        cnt[uu] = min(kept, p.topk);
+        cnt[kUT + buf * kUT + uu] = 0;
+      }
+      return;
+    }
 #pragma unroll
     for (int t = 0; t < kLT; ++t) {
       const int i = min(lane + 64 * t, kMaxTopk - 1);
@@ -808,6 +940,7 @@ __global__ __launch_bounds__(kThreads) void rk_fused(RkParams p) {
   // different rows); a user past U takes the last user's and a group outside [0, G) is clamped, so
   // no address leaves the table
   auto prior_row = [&](int t) -> const float* {
+    if constexpr (CAP) if (p.bias == nullptr) return nullptr;   // (the capped form without a prior)
     const int bu = min(MODE == kPair ? t : t * kUT + uu, p.U - 1);
     int g = 0;
     if (p.grp != nullptr) g = (int)rk_sload(reinterpret_cast<const uint32_t*>(p.grp) + bu);
@@ -828,7 +961,7 @@ __global__ __launch_bounds__(kThreads) void rk_fused(RkParams p) {
 #pragma unroll
     for (int nt = 0; nt < 2; ++nt) {
       const int n = SUB ? idn[nt] : news_step(s) * kNT + 64 * nsub + 32 * nt + (lane & 31);
-      pnx[nt] = (SUB ? n >= 0 : n < N) ? prow[n] : 0.f;
+      pnx[nt] = (!CAP || p.bias != nullptr) && (SUB ? n >= 0 : n < N) ? prow[n] : 0.f;
     }
   };
   if constexpr (BIAS) {                           // the first step's (complete behind the first chunk's wait)
@@ -1001,7 +1134,7 @@ __global__ __launch_bounds__(kThreads) void rk_fused(RkParams p) {
                 if (32 * kt + 16 * h + e < K) sm += acc[kt][nt][e];
             score = xor32_sum(sm) / (float)K;            // model.py:130-131
           }
-          if constexpr (BIAS) score = rk_add_rn(score, pri[nt]);
+          if constexpr (BIAS) if (!CAP || p.bias != nullptr) score = rk_add_rn(score, pri[nt]);
           if constexpr (MODE == kCount) {
             // Lane j holds the key of target j of user uu (a slot past T: the greatest key); lanes
             // 0..31 hold the scores of news n0 + lane. The 32 score keys are broadcast in turn
@@ -1174,14 +1307,22 @@ __global__ __launch_bounds__(256) void rk_merge(const float* __restrict__ ws_s, 
 // [0, 256), b at [256, 512), a dropped entry's id -1), eight slots per lane, ranked by counting
 // the entries better than each (equal (score, id) pairs of one list: the lower slot first, so the
 // ranks are distinct whatever the input).
+// CAP (a compile-time switch: the plain merge is the code it was): then the capped walk over what is
+// left. The cluster ids (clus [n_clus]; an id at or past n_clus is in no cluster and no word is read
+// for it) are loaded after the drop and replace steps; per entry rc = the better entries of its own
+// cluster, kept iff unclustered or rc < cap; an entry's rank = the better KEPT entries; the
+// (-inf, -1) tail follows the kept count.
+template <bool CAP>
 __global__ __launch_bounds__(64 * kMergeUsers) void topk_merge(const float* __restrict__ a_s, const int32_t* __restrict__ a_i,
                                                                int ka, const float* __restrict__ b_s,
                                                                const int32_t* __restrict__ b_i, int kb, int U, int topk,
                                                                const uint32_t* __restrict__ ok, int N,
-                                                               float* __restrict__ out_s, int32_t* __restrict__ out_i) {
+                                                               float* __restrict__ out_s, int32_t* __restrict__ out_i,
+                                                               const int32_t* __restrict__ clus, int n_clus, int cap) {
   constexpr int kSlots = 2 * kMaxTopk, kPer = kSlots / 64;
   __shared__ float ms[kMergeUsers][kSlots];
   __shared__ int mi[kMergeUsers][kSlots];
+  [[maybe_unused]] __shared__ int mg[CAP ? kMergeUsers : 1][CAP ? kSlots : 1];
   const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const int user = blockIdx.x * kMergeUsers + w;
   if (user >= U) return;                   // wave-uniform; no block barrier below
@@ -1221,6 +1362,41 @@ __global__ __launch_bounds__(64 * kMergeUsers) void topk_merge(const float* __re
   }
   __builtin_amdgcn_s_waitcnt(0);
   __builtin_amdgcn_wave_barrier();
+  if constexpr (CAP) {
+    // the cap: an entry with cap or more better entries of its own cluster leaves (its id becomes
+    // -1, as a pruned entry's), then the ranking below runs over the kept entries alone
+    int g[kPer], rc[kPer];
+#pragma unroll
+    for (int t = 0; t < kPer; ++t) {
+      g[t] = id[t] >= 0 && id[t] < n_clus ? max(clus[id[t]], -1) : -1;
+      mg[w][lane + 64 * t] = g[t];
+      rc[t] = 0;
+    }
+    __builtin_amdgcn_s_waitcnt(0);
+    __builtin_amdgcn_wave_barrier();
+    for (int half = 0; half < 2; ++half) {
+      const int j0 = half * kMaxTopk, j1 = j0 + (half ? kb : ka);
+      for (int j = j0; j < j1; ++j) {
+        const int i2 = mi[w][j], g2 = mg[w][j];
+        if (i2 < 0 || g2 < 0) continue;      // wave-uniform
+        const float s2 = ms[w][j];
+#pragma unroll
+        for (int t = 0; t < kPer; ++t)
+          rc[t] += g[t] == g2 && (better(s2, i2, sv[t], id[t]) || (s2 == sv[t] && i2 == id[t] && j < lane + 64 * t)) ? 1 : 0;
+      }
+    }
+    __builtin_amdgcn_s_waitcnt(0);
+    __builtin_amdgcn_wave_barrier();          // every read of the ids comes before the first write
+#pragma unroll
+    for (int t = 0; t < kPer; ++t) {
+      if (g[t] >= 0 && rc[t] >= cap) {
+        id[t] = -1;
+        mi[w][lane + 64 * t] = -1;
+      }
+    }
+    __builtin_amdgcn_s_waitcnt(0);
+    __builtin_amdgcn_wave_barrier();
+  }
   int rank[kPer];
 #pragma unroll
   for (int t = 0; t < kPer; ++t) rank[t] = 0;
@@ -1335,8 +1511,36 @@ int rk_launch_geo(void* stream, const RkParams& prm, bool split) {
   return e == hipSuccess ? MINER_OK : (int)e;
 }
 
+// the capped form (CAP): unsplit, filtered (either filter may be null), on the biased instantiation
+// with the prior tested at run time — two kernels per shape (table / subset), not four; the chunk
+// count and K compile-time by rk_launch_geo's rule. A workspace is never written.
+template <class T, int NKT, int S, bool SUB>
+int rk_launch_cap(void* stream, const RkParams& prm) {
+  void (*kern)(RkParams) = rk_fused<T, NKT, S, 0, 1, 0, 0, true, SUB, kRank, true, true>;
+  if constexpr (sizeof(T) == 2) {
+    constexpr int kN768 = 768 * 2 / kRB<0>;
+    if (prm.d == 768) {
+      kern = rk_fused<T, NKT, S, kN768, 1, 0, 0, true, SUB, kRank, true, true>;
+      if constexpr (NKT == 2)
+        if (prm.K == 64) kern = rk_fused<T, NKT, S, kN768, 1, 0, 64, true, SUB, kRank, true, true>;
+    }
+  }
+  constexpr int NR = S == MINER_SCORE_WEIGHTED ? 2 * NKT : NKT;
+  const int lds = RkLds<NR, 0, true, true>::kTotal;
+  static_assert(RkLds<NR, 0, true, true>::kTotal <= 160 * 1024, "ranker LDS (the capped form: exclusion lists and cluster ids)");
+  hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+  if (e != hipSuccess) return (int)e;
+  const int ntiles = (prm.U + kUT - 1) / kUT;
+  const int grid = num_cus() < ntiles ? num_cus() : ntiles;
+  hipLaunchKernelGGL(kern, dim3(grid), dim3(kThreads), lds, static_cast<hipStream_t>(stream), prm);
+  e = hipGetLastError();
+  return e == hipSuccess ? MINER_OK : (int)e;
+}
+
 template <class T, int NKT, int S>
 int rk_launch(void* stream, const RkParams& prm) {
+  if (prm.clus != nullptr)
+    return prm.ids != nullptr ? rk_launch_cap<T, NKT, S, true>(stream, prm) : rk_launch_cap<T, NKT, S, false>(stream, prm);
   const bool split = rk_split(prm);
   const bool flt = prm.ok != nullptr || prm.E > 0;     // the filtered instantiation only when asked for
   // the subset form: one instantiation per shape, the filtered one (either filter may be null),
@@ -1417,6 +1621,14 @@ int bias_check(const float* news_bias, int G, const int32_t* user_group) {
   return MINER_OK;
 }
 
+// the cluster table's checks, shared by the two capped entry points (after each one's own); cap is
+// read only with a table
+int cap_check(const int32_t* news_cluster, int cap) {
+  if (news_cluster != nullptr && cap <= 0) return MINER_EINVAL;
+  if (news_cluster != nullptr && cap > kMaxTopk) return MINER_ESHAPE;
+  return MINER_OK;
+}
+
 template <class T>
 int rk_dispatch(void* stream, const RkParams& prm) {
   const int st = prm.score_type;
@@ -1442,7 +1654,8 @@ int check_dims(int dtype, int d, int Dc, int K) {
 int rk_run(void* stream, int dtype, int score_type, const void* user_mui, const void* user_proj, const void* news, int U,
            int N, int d, int K, int topk, const int32_t* exclude_ids, int E, const uint32_t* news_ok, bool subset,
            const int32_t* news_ids, int M, float* top_scores, int32_t* top_ids, void* workspace, size_t workspace_bytes,
-           const float* news_bias = nullptr, int G = 0, const int32_t* user_group = nullptr) {
+           const float* news_bias = nullptr, int G = 0, const int32_t* user_group = nullptr,
+           const int32_t* news_cluster = nullptr, int cap = 0) {
   const int ck = check_dims(dtype, d, 1, K);
   if (ck != MINER_OK) return ck;
   if (score_type < MINER_SCORE_WEIGHTED || score_type > MINER_SCORE_MEAN) return MINER_EINVAL;
@@ -1460,6 +1673,9 @@ int rk_run(void* stream, int dtype, int score_type, const void* user_mui, const 
   }
   const int bk = bias_check(news_bias, G, user_group);
   if (bk != MINER_OK) return bk;
+  const int cc = cap_check(news_cluster, cap);
+  if (cc != MINER_OK) return cc;
+  if (!aligned4(news_cluster)) return MINER_EALIGN;
   if (U == 0) return MINER_OK;
   RkParams prm{};
   if (!aligned16(workspace)) return MINER_EALIGN;
@@ -1480,6 +1696,7 @@ int rk_run(void* stream, int dtype, int score_type, const void* user_mui, const 
   prm.excl = E > 0 ? exclude_ids : nullptr; prm.E = E; prm.ok = news_ok;
   prm.ids = subset ? news_ids : nullptr; prm.M = subset ? M : 0;
   prm.bias = news_bias; prm.grp = news_bias ? user_group : nullptr; prm.G = news_bias ? G : 0;
+  prm.clus = news_cluster; prm.cap = news_cluster ? cap : 0;
   if (dtype == MINER_DTYPE_BF16) return rk_dispatch<__bf16>(stream, prm);
   if (dtype == MINER_DTYPE_F16) return rk_dispatch<_Float16>(stream, prm);
   return rk_dispatch<float>(stream, prm);
@@ -1652,9 +1869,27 @@ int miner_rank_topk_biased(void* stream, int dtype, int score_type, const void* 
                 user_group);
 }
 
+int miner_rank_topk_capped(void* stream, int dtype, int score_type, const void* user_mui, const void* user_proj,
+                           const void* news, int U, int N, int d, int K, int topk, const int32_t* exclude_ids, int E,
+                           const uint32_t* news_ok, const int32_t* news_ids, int M, float* top_scores, int32_t* top_ids,
+                           void* workspace, size_t workspace_bytes, const float* news_bias, int G,
+                           const int32_t* user_group, const int32_t* news_cluster, int cap) {
+  const bool table = news_ids == nullptr && M < 0;     // the whole table: the filtered form
+  return rk_run(stream, dtype, score_type, user_mui, user_proj, news, U, N, d, K, topk, exclude_ids, E, news_ok, !table,
+                table ? nullptr : news_ids, table ? 0 : M, top_scores, top_ids, workspace, workspace_bytes, news_bias, G,
+                user_group, news_cluster, cap);
+}
+
 int miner_topk_merge(void* stream, const float* a_scores, const int32_t* a_ids, int ka, const float* b_scores,
                      const int32_t* b_ids, int kb, int U, int topk, const uint32_t* news_ok, int N, float* out_scores,
                      int32_t* out_ids) {
+  return miner_topk_merge_capped(stream, a_scores, a_ids, ka, b_scores, b_ids, kb, U, topk, news_ok, N, out_scores, out_ids,
+                                 nullptr, 0, 0);
+}
+
+int miner_topk_merge_capped(void* stream, const float* a_scores, const int32_t* a_ids, int ka, const float* b_scores,
+                            const int32_t* b_ids, int kb, int U, int topk, const uint32_t* news_ok, int N,
+                            float* out_scores, int32_t* out_ids, const int32_t* news_cluster, int n_cluster, int cap) {
   if (U < 0 || ka < 0 || kb < 0 || topk <= 0) return MINER_EINVAL;
   if (ka > kMaxTopk || kb > kMaxTopk || topk > kMaxTopk) return MINER_ESHAPE;
   if ((ka > 0 && (!a_scores || !a_ids)) || (kb > 0 && (!b_scores || !b_ids)) || !out_scores || !out_ids) return MINER_EINVAL;
@@ -1662,10 +1897,17 @@ int miner_topk_merge(void* stream, const float* a_scores, const int32_t* a_ids, 
   if (!aligned4(a_scores) || !aligned4(a_ids) || !aligned4(b_scores) || !aligned4(b_ids) || !aligned4(news_ok) ||
       !aligned4(out_scores) || !aligned4(out_ids))
     return MINER_EALIGN;
+  const int cc = cap_check(news_cluster, cap);
+  if (cc != MINER_OK) return cc;
+  if (news_cluster != nullptr && n_cluster <= 0) return MINER_EINVAL;
+  if (!aligned4(news_cluster)) return MINER_EALIGN;
   if (U == 0) return MINER_OK;
-  hipLaunchKernelGGL(topk_merge, dim3((U + kMergeUsers - 1) / kMergeUsers), dim3(64 * kMergeUsers), 0,
+  // (the capped instantiation only with a table: the plain merge launches the kernel it did)
+  void (*kern)(const float*, const int32_t*, int, const float*, const int32_t*, int, int, int, const uint32_t*, int, float*,
+               int32_t*, const int32_t*, int, int) = news_cluster != nullptr ? topk_merge<true> : topk_merge<false>;
+  hipLaunchKernelGGL(kern, dim3((U + kMergeUsers - 1) / kMergeUsers), dim3(64 * kMergeUsers), 0,
                      static_cast<hipStream_t>(stream), a_scores, a_ids, ka, b_scores, b_ids, kb, U, topk, news_ok, N,
-                     out_scores, out_ids);
+                     out_scores, out_ids, news_cluster, n_cluster, cap);
   const hipError_t e = hipGetLastError();
   return e == hipSuccess ? MINER_OK : (int)e;
 }

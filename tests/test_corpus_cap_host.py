@@ -1,0 +1,189 @@
+"""The per-cluster cap entry points on the host: miner_rank_topk_capped and miner_topk_merge_capped
+are exported and declared, the cluster table's argument errors (include/miner_corpus.h) are answered
+with their codes after the base call's own checks and before any launch — with U = 0 where the
+arguments are accepted, so nothing launches —, and the ABI number is unchanged. The Python-side
+argument errors of news_cluster= / cluster_cap= are raised before anything touches a device. The
+AddressSanitizer driver of the two entry points (tests/native/abi_errors_cap.cpp, a stand-alone
+program) runs as tests/test_corpus_bias_host.py runs its own. No compute call is made (runs on
+CPU-only machines)."""
+import ctypes
+import inspect
+import os
+import subprocess
+
+import pytest
+import torch
+
+from miner_amd import _lib, build, corpus
+
+OK, EINVAL, ESHAPE, EALIGN = 0, -1, -2, -3
+F32, WEIGHTED = _lib.DTYPE_F32, _lib.SCORE_WEIGHTED
+P = ctypes.c_void_p
+NAMES = ("miner_rank_topk_capped", "miner_topk_merge_capped")
+
+
+@pytest.fixture(scope="module")
+def lib():
+    if not os.path.exists(_lib.LIB_PATH):
+        build.build_library()
+    return _lib.lib()
+
+
+def p(v):
+    return None if v is None else P(v)
+
+
+def topk(lib, *, clus=112, cap=2, bias=None, G=0, grp=None, ids=None, M=-1, excl=16, E=2, ok=48, U=0, N=100, K=32, d=64,
+         k=10, mui=16, proj=16, news=16, dtype=F32, st=WEIGHTED, out_s=32, out_i=64, ws=None):
+    return lib.miner_rank_topk_capped(None, dtype, st, p(mui), p(proj), p(news), U, N, d, K, k, p(excl), E, p(ok), p(ids), M,
+                                      p(out_s), p(out_i), p(ws), 0, p(bias), G, p(grp), p(clus), cap)
+
+
+def merge(lib, *, clus=112, n=100, cap=2, a_s=16, a_i=32, ka=10, b_s=48, b_i=64, kb=10, U=0, k=10, ok=80, N=100, out_s=96,
+          out_i=128):
+    return lib.miner_topk_merge_capped(None, p(a_s), p(a_i), ka, p(b_s), p(b_i), kb, U, k, p(ok), N, p(out_s), p(out_i),
+                                       p(clus), n, cap)
+
+
+def test_symbols_are_exported(lib):
+    raw = ctypes.CDLL(_lib.LIB_PATH)
+    for name in NAMES:
+        assert name in _lib.SIGNATURES
+        assert ctypes.cast(getattr(raw, name), ctypes.c_void_p).value
+    assert lib.miner_abi_version() == 6 == _lib.ABI_VERSION      # the entry points are additive
+    I, V = ctypes.c_int, ctypes.c_void_p
+    assert _lib.SIGNATURES["miner_rank_topk_capped"] == (I, _lib.SIGNATURES["miner_rank_topk_biased"][1] + [V, I])
+    assert _lib.SIGNATURES["miner_topk_merge_capped"] == (I, _lib.SIGNATURES["miner_topk_merge"][1] + [V, I, I])
+    for name in ("rank_topk", "rank_corpus", "merge_topk", "update_topk"):
+        params = inspect.signature(getattr(corpus, name)).parameters
+        for kw in ("news_cluster", "cluster_cap"):
+            assert params[kw].kind is inspect.Parameter.KEYWORD_ONLY and params[kw].default is None, (name, kw)
+    params = inspect.signature(corpus.cap_topk).parameters
+    assert list(params) == ["lists", "news_cluster", "cluster_cap", "topk"] and params["topk"].default is None
+    # not offered under caps: their signatures are the ones they had
+    for name in ("rank_of", "evaluate_corpus", "score_pairs", "rescore_topk"):
+        params = inspect.signature(getattr(corpus, name)).parameters
+        assert "news_cluster" not in params and "cluster_cap" not in params, name
+
+
+def test_cap_argument_errors_in_order_before_any_launch(lib):
+    for U in (0, 3):                                             # with users too: still no launch
+        for form in (topk, merge):
+            assert form(lib, U=U, cap=0) == EINVAL               # a table with no room
+            assert form(lib, U=U, cap=-2) == EINVAL
+            assert form(lib, U=U, cap=corpus.MAX_TOPK + 1) == ESHAPE
+            assert form(lib, U=U, clus=114) == EALIGN            # 4-byte alignment
+            assert form(lib, U=U, clus=114, cap=0) == EINVAL     # cap, then the alignment
+            assert form(lib, U=U, clus=114, cap=1000) == ESHAPE
+        assert merge(lib, U=U, n=0) == EINVAL                    # a table without entries
+        assert merge(lib, U=U, n=-5) == EINVAL
+        assert merge(lib, U=U, n=0, cap=257) == ESHAPE           # cap, then n_cluster
+        assert merge(lib, U=U, n=0, clus=114) == EINVAL          # n_cluster, then the alignment
+    # accepted argument sets: U = 0 returns after the validation, nothing launches
+    for form in (topk, merge):
+        assert form(lib) == OK
+        assert form(lib, cap=1) == OK
+        assert form(lib, cap=corpus.MAX_TOPK, clus=116) == OK    # 4-byte, not 16-byte, aligned
+        assert form(lib, clus=None, cap=0) == OK                 # no table: the base call
+        assert form(lib, clus=None, cap=-9) == OK                # cap is read only with a table
+        assert form(lib, clus=None, cap=10 ** 6) == OK
+    assert merge(lib, clus=None, n=-1) == OK
+    assert merge(lib, n=1) == OK
+    assert topk(lib, bias=80, G=3, grp=96) == OK                 # with a prior
+    assert topk(lib, ids=16, M=5) == OK                          # the subset form
+    assert topk(lib, ids=16, M=0) == OK
+    assert topk(lib, ws=256) == OK                               # a workspace is accepted
+
+
+def test_the_base_checks_still_come_first(lib):
+    bad = dict(clus=114, cap=0)                                  # every cap argument invalid as well
+    assert topk(lib, dtype=9, **bad) == EINVAL
+    assert topk(lib, K=65, **bad) == ESHAPE
+    assert topk(lib, d=100, **bad) == ESHAPE
+    assert topk(lib, st=7, **bad) == EINVAL
+    assert topk(lib, U=-1, **bad) == EINVAL
+    assert topk(lib, N=0, **bad) == EINVAL
+    assert topk(lib, mui=None, **bad) == EINVAL
+    assert topk(lib, proj=None, **bad) == EINVAL                 # weighted needs the projection
+    assert topk(lib, news=20, **bad) == EALIGN
+    assert topk(lib, k=0, **bad) == EINVAL
+    assert topk(lib, k=corpus.MAX_TOPK + 1, **bad) == ESHAPE
+    assert topk(lib, E=-1, **bad) == EINVAL
+    assert topk(lib, E=corpus.MAX_L + 1, **bad) == ESHAPE
+    assert topk(lib, excl=18, **bad) == EALIGN
+    assert topk(lib, ok=50, **bad) == EALIGN
+    assert topk(lib, ids=16, M=-1, **bad) == EINVAL              # the subset rules
+    assert topk(lib, ids=None, M=4, **bad) == EINVAL
+    assert topk(lib, ids=18, M=4, **bad) == EALIGN
+    assert topk(lib, bias=80, G=0, **bad) == EINVAL              # the prior's checks
+    assert topk(lib, bias=None, grp=96, **bad) == EINVAL
+    assert topk(lib, bias=82, G=1, clus=112, cap=257) == EALIGN
+    bad = dict(clus=114, cap=0, n=0)
+    assert merge(lib, U=-1, **bad) == EINVAL
+    assert merge(lib, ka=-1, **bad) == EINVAL
+    assert merge(lib, k=0, **bad) == EINVAL
+    assert merge(lib, kb=corpus.MAX_TOPK + 1, **bad) == ESHAPE
+    assert merge(lib, k=corpus.MAX_TOPK + 1, **bad) == ESHAPE
+    assert merge(lib, a_i=None, **bad) == EINVAL
+    assert merge(lib, out_s=None, **bad) == EINVAL
+    assert merge(lib, N=0, **bad) == EINVAL                      # a bitmap with N <= 0
+    assert merge(lib, b_s=50, clus=112, cap=257) == EALIGN
+    assert merge(lib, ok=82, clus=112, cap=257) == EALIGN
+
+
+def test_python_argument_errors():
+    U, K, d, N = 3, 4, 64, 50
+    mui = torch.zeros(U, K, d)
+    tab = torch.zeros(N, d)
+    ids = torch.zeros(U, 5, dtype=torch.int64)
+    lists = (torch.zeros(U, 5), ids)
+    clus = torch.arange(N) % 4
+    calls = {
+        "rank_topk": lambda **kw: corpus.rank_topk(mui, mui, tab, 5, **kw),
+        "update_topk": lambda **kw: corpus.update_topk(lists, mui, mui, tab, ids[0], **kw),
+        "merge_topk": lambda **kw: corpus.merge_topk(lists, lists, 5, **kw),
+        "cap_topk": lambda news_cluster=None, cluster_cap=None: corpus.cap_topk(lists, news_cluster, cluster_cap),
+    }
+    L = 6
+    hid, mask = torch.zeros(U, L, dtype=torch.int32), torch.ones(U, L, dtype=torch.bool)
+    pk = corpus.EncoderWeights(torch.zeros(16, dtype=torch.uint8), torch.float32, d, 8, K, True)
+    calls["rank_corpus"] = lambda **kw: corpus.rank_corpus(tab, hid, mask, pk, 5, **kw)
+    for name, call in calls.items():
+        table_len = name in ("rank_topk", "update_topk", "rank_corpus")    # the table's length is N there
+        with pytest.raises(ValueError):
+            call(news_cluster=clus)                               # one without the other
+        with pytest.raises(ValueError):
+            call(cluster_cap=2)
+        for bad in (0, -1, corpus.MAX_TOPK + 1, 2.0, "2", True, torch.tensor(2)):
+            with pytest.raises(ValueError):
+                call(news_cluster=clus, cluster_cap=bad)
+        wrong = [clus.float(), clus == 0, clus[None, :], clus.view(N, 1), [0] * N, torch.zeros(0, dtype=torch.int64),
+                 torch.tensor([0, 2 ** 31] + [0] * (N - 2)), torch.tensor([0, -2 ** 31 - 1] + [0] * (N - 2))]
+        if table_len:
+            wrong += [clus[:N - 1], torch.cat([clus, clus])]
+        for bad in wrong:
+            with pytest.raises(ValueError):
+                call(news_cluster=bad, cluster_cap=2)
+        # well-formed, but not on a GPU: no CPU path
+        for kw in (dict(news_cluster=clus, cluster_cap=1), dict(news_cluster=clus.int(), cluster_cap=corpus.MAX_TOPK),
+                   dict(news_cluster=(clus - 1).to(torch.int16), cluster_cap=3),
+                   dict(news_cluster=torch.tensor([2 ** 31 - 1, -2 ** 31] + [0] * (N - 2)), cluster_cap=3)):
+            with pytest.raises(RuntimeError):
+                call(**kw)
+
+
+@pytest.fixture(scope="module")
+def driver():
+    try:
+        return build.build_asan_driver_cap()
+    except RuntimeError as e:                       # no ROCm toolchain in this environment
+        pytest.skip(f"asan build unavailable: {e}")
+
+
+def test_new_entry_points_under_asan(driver):
+    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=0:abort_on_error=0:halt_on_error=1")
+    res = subprocess.run([driver], capture_output=True, text=True, timeout=300, env=env)
+    out = res.stdout + res.stderr
+    assert "AddressSanitizer" not in out, out[-4000:]
+    assert res.returncode == 0, out[-4000:]
+    assert "0 failures" in res.stdout, out[-2000:]
