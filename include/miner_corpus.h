@@ -291,6 +291,44 @@ int miner_topk_merge_capped(void* stream, const float* a_scores, const int32_t* 
                             const uint32_t* news_ok, int N, float* out_scores, int32_t* out_ids,
                             const int32_t* news_cluster, int n_cluster, int cap);
 
+/*
+ * Keyset cursors: a user's ranking continued after a given entry, for lists of any depth as pages of
+ * up to MINER_CORPUS_MAX_TOPK entries that each stream the table once.
+ *   after_scores [U] fp32, after_ids [U] int32, device pointers, 4-byte aligned, both or neither.
+ * The ranking order is the ranker's strict total order: score descending, then lower news id, where
+ * the score is the value that is ranked (the biased sum under news_bias) and the id the table id
+ * (also in the subset form). User u's list holds the first topk entries of its ranking — under the
+ * same exclude_ids, news_ok, news_ids and news_bias — that come STRICTLY AFTER the pair
+ * (after_scores[u], after_ids[u]): score < after_scores[u], or score == after_scores[u] (a float
+ * compare: -0 equals +0) and id > after_ids[u]; then (-inf, -1). A listed entry carries, bit for bit,
+ * the score of the call without a cursor. Passing each row's last entry back continues the ranking
+ * where that row ended; the pages of a user are disjoint and concatenate to its complete ranking.
+ *   (+inf, -1)        "before everything": every listable entry comes after it (the first page).
+ *   (-inf, 2^31 - 1)  "after everything": nothing comes after it. NOT the (-inf, -1) tail of a short
+ *                     row: a cursor there would list the news that score -inf once more.
+ *   a NaN score       lists nothing.
+ * The cursor need not be a listed news: an id that is excluded, ineligible, outside news_ids,
+ * negative or past N is a position in the order like any other. Split and unsplit forms agree bit
+ * for bit (every slice applies the cursor). There is no cursor under caps: a capped walk also needs
+ * the per-cluster counts of the earlier pages, which a (score, id) pair does not carry.
+ *
+ * miner_rank_topk_after: miner_rank_topk_capped's arguments, then the two above. With both NULL it
+ * returns exactly what miner_rank_topk_capped returns on the other arguments (it launches the same
+ * kernel). With a cursor the cursor form of the ranker runs, over the table or the id list, split or
+ * unsplit, with any of exclude_ids, news_ok and news_bias NULL or not; a call without a cursor
+ * launches no code of it. After the capped call's own checks, in their order and with
+ * their codes: one of after_scores / after_ids NULL and the other not: MINER_EINVAL; a cursor with
+ * a non-NULL news_cluster: MINER_EINVAL; a misaligned after_scores or after_ids: MINER_EALIGN (all
+ * before any launch, and before the U == 0 return).
+ */
+int miner_rank_topk_after(void* stream, int dtype, int score_type, const void* user_mui,
+                          const void* user_proj, const void* news, int U, int N, int d, int K, int topk,
+                          const int32_t* exclude_ids, int E, const uint32_t* news_ok,
+                          const int32_t* news_ids, int M, float* top_scores, int32_t* top_ids,
+                          void* workspace, size_t workspace_bytes, const float* news_bias, int G,
+                          const int32_t* user_group, const int32_t* news_cluster, int cap,
+                          const float* after_scores, const int32_t* after_ids);
+
 #ifdef __cplusplus
 }
 #endif

@@ -122,6 +122,7 @@ ASAN_DRIVER_SUBSET = os.path.join(ROOT, "tests", "native", "abi_errors_subset.cp
 ASAN_DRIVER_RANK = os.path.join(ROOT, "tests", "native", "abi_errors_rank.cpp")
 ASAN_DRIVER_BIAS = os.path.join(ROOT, "tests", "native", "abi_errors_bias.cpp")
 ASAN_DRIVER_CAP = os.path.join(ROOT, "tests", "native", "abi_errors_cap.cpp")
+ASAN_DRIVER_AFTER = os.path.join(ROOT, "tests", "native", "abi_errors_after.cpp")
 
 
 def build_asan_driver(force: bool = False, verbose: bool = False, driver: str = ASAN_DRIVER) -> str:
@@ -192,6 +193,12 @@ def build_asan_driver_cap(force: bool = False, verbose: bool = False) -> str:
     return build_asan_driver(force=force, verbose=verbose, driver=ASAN_DRIVER_CAP)
 
 
+def build_asan_driver_after(force: bool = False, verbose: bool = False) -> str:
+    """build/asan/abi_errors_after: the error paths of miner_rank_topk_after
+    (tests/native/abi_errors_after.cpp; run by tests/test_corpus_after_host.py)."""
+    return build_asan_driver(force=force, verbose=verbose, driver=ASAN_DRIVER_AFTER)
+
+
 if __name__ == "__main__":
     if "--asan" in sys.argv:
         print(build_asan_driver(force="--force" in sys.argv, verbose=True))
@@ -199,5 +206,6 @@ if __name__ == "__main__":
         print(build_asan_driver_rank(verbose=True))
         print(build_asan_driver_bias(verbose=True))
         print(build_asan_driver_cap(verbose=True))
+        print(build_asan_driver_after(verbose=True))
     else:
         print(build_library(force="--force" in sys.argv, verbose=True, debug="--debug" in sys.argv))

@@ -15,6 +15,9 @@ d=768, fp16), backed by libminer_hip.so (include/miner_corpus.h).
     rank_topk(..., news_bias=prior)                        # fp32 [N] or [G, N] (+ user_group [U]) added to the
                                                            # click score before it ranks; also score_pairs, rank_of,
                                                            # update_topk, rescore_topk, rank_corpus, evaluate_corpus
+    page2 = rank_topk(..., after=page_cursor(page1))       # keyset cursors: the ranking continued strictly after
+                                                           # (score, id) per user; start_cursor, page_cursor;
+    deep = rank_topk_deep(mui, proj, news_table, 1000)     # any depth, ceil(topk / 256) pages side by side
     rank_topk(..., news_cluster=story, cluster_cap=1)      # at most cluster_cap news of one cluster (int [N], < 0:
                                                            # none) per list, inside the ranker's merge; also merge_topk,
                                                            # update_topk, rank_corpus; cap_topk(lists, story, 1) caps a
@@ -254,10 +257,81 @@ def _caps(news_cluster, cluster_cap, N: Optional[int]) -> Optional[_Caps]:
     return _Caps(_contig(news_cluster, torch.int32), cluster_cap)
 
 
+@dataclasses.dataclass
+class _Cursor:
+    """Checked keyset cursors: scores fp32 [U] and ids int32 [U], contiguous on the device."""
+    scores: Tensor
+    ids: Tensor
+
+    def users(self, u0: int, u1: int) -> "_Cursor":
+        return _Cursor(self.scores[u0:u1], self.ids[u0:u1])
+
+
+_INT32_MAX = 2 ** 31 - 1
+
+
+def _cursor(after, U: int) -> Optional[_Cursor]:
+    """after= of the ranking entries -> a _Cursor, or None without one. Shapes and dtypes are checked
+    before anything touches the device; ids of a dtype wider than int32 must fit int32."""
+    if after is None:
+        return None
+    if isinstance(after, _Cursor):
+        if after.scores.shape[0] != U:
+            raise ValueError(f"the cursor was made for {after.scores.shape[0]} users, not {U}")
+        return after
+    try:
+        s, i = after
+    except (TypeError, ValueError):
+        raise ValueError("after must be a (scores, ids) pair")
+    if not isinstance(s, Tensor) or s.dtype != torch.float32 or s.dim() != 1 or s.shape[0] != U:
+        raise ValueError(f"after: the scores must be a float32 [{U}] tensor")
+    if not isinstance(i, Tensor) or i.dim() != 1 or i.shape[0] != U or i.is_floating_point() or i.is_complex() \
+            or i.dtype == torch.bool:
+        raise ValueError(f"after: the ids must be an integer [{U}] tensor")
+    if i.dtype not in (torch.int32, torch.int16, torch.int8, torch.uint8) and U:
+        if int(i.min()) < -2 ** 31 or int(i.max()) > _INT32_MAX:
+            raise ValueError("after: the ids must fit int32")
+    _require_device(s, i)
+    return _Cursor(s.contiguous(), _contig(i, torch.int32))
+
+
+def _no_cursor_under_caps(after, news_cluster, cluster_cap) -> None:
+    """A capped walk also needs the earlier pages' per-cluster counts, which a (score, id) pair does
+    not carry: a cursor together with caps is an argument error, whatever else is wrong with either."""
+    if after is not None and (news_cluster is not None or cluster_cap is not None):
+        raise ValueError("after= cannot be combined with news_cluster / cluster_cap")
+
+
+def start_cursor(U: int, device):
+    """The cursor before everything, (+inf, -1) for each of U users: rank_topk(after=start_cursor(...))
+    is the first page — the list of the call without a cursor."""
+    return (torch.full((U,), float("inf"), dtype=torch.float32, device=device),
+            torch.full((U,), -1, dtype=torch.int32, device=device))
+
+
+def page_cursor(lists):
+    """The cursor that continues ``lists`` = (scores [U,k], ids [U,k]), a page rank_topk returned:
+    per row its last entry if the row is full, else (-inf, 2^31 - 1), "after everything" — a short
+    row means the ranking ended. (Not the (-inf, -1) tail itself: a cursor there would list the news
+    that score -inf once more.) Pure tensor operations on the lists' device, no host synchronisation."""
+    try:
+        s, i = lists
+    except (TypeError, ValueError):
+        raise ValueError("lists must be a (scores, ids) pair")
+    if not isinstance(s, Tensor) or not isinstance(i, Tensor) or s.dim() != 2 or s.shape != i.shape or s.shape[1] < 1 \
+            or not s.is_floating_point() or i.is_floating_point() or i.dtype == torch.bool:
+        raise ValueError("lists: scores [U,k] and integer ids [U,k] of one shape, k >= 1")
+    last_s, last_i = s[:, -1].to(torch.float32), i[:, -1]
+    full = last_i >= 0
+    return (torch.where(full, last_s, float("-inf")).contiguous(),
+            torch.where(full, last_i, _INT32_MAX).to(torch.int32).contiguous())
+
+
 def rank_topk(user_mui: Tensor, user_proj: Optional[Tensor], news: Tensor, topk: int, *,
               score_type: str = "weighted", exclude_ids: Optional[Tensor] = None,
               eligible: Optional[Tensor] = None, news_ids=None, news_bias=None,
-              user_group: Optional[Tensor] = None, news_cluster=None, cluster_cap: Optional[int] = None):
+              user_group: Optional[Tensor] = None, news_cluster=None, cluster_cap: Optional[int] = None,
+              after=None):
     """Top-k news per user by the click score, best first: (scores [U,topk] fp32, ids [U,topk]
     int32); entries past the table size are (-inf, -1).
 
@@ -291,9 +365,24 @@ def rank_topk(user_mui: Tensor, user_proj: Optional[Tensor], news: Tensor, topk:
     entries ((-inf, -1) after a shorter one). Scores are the uncapped call's, bit for bit; an
     excluded or ineligible news uses up no cap. The capped ranker has no split form: a batch of
     U <= 510 users runs the unsplit kernel (MINER_RK_SPLIT is ignored), at the price
-    profiles/rk_cap_ab.txt records. With both None the call is today's."""
+    profiles/rk_cap_ab.txt records. With both None the call is today's.
+
+    after: a keyset cursor, (scores [U] float32, ids [U] integer) on the device — start_cursor,
+    page_cursor of an earlier page, or any pair. The list then holds the first topk entries of the
+    user's ranking (score descending, then lower id; under every other argument) that come strictly
+    after (scores[u], ids[u]): a lower score, or an equal one (a float compare: -0 equals +0) with a
+    higher id. The score compared is the one ranked (the biased sum under a prior), the id the table
+    id. Listed scores are those of the call without a cursor, bit for bit, and the pages chained with
+    page_cursor are disjoint and concatenate to the complete ranking. (+inf, -1) is before
+    everything, (-inf, 2^31 - 1) after everything, a NaN score lists nothing, and the cursor need not
+    be a listed, eligible or existing news: it is a position in the order. Each page streams the
+    table once (the price: profiles/rk_after_ab.txt). There is no cursor under caps (a capped walk
+    also needs the earlier pages' per-cluster counts): ``after`` with news_cluster / cluster_cap
+    raises ValueError. Without ``after`` the call is today's."""
+    _no_cursor_under_caps(after, news_cluster, cluster_cap)
     pri = _prior(news_bias, user_group, user_mui.shape[0], news.shape[0])
     caps = _caps(news_cluster, cluster_cap, news.shape[0])
+    cur = _cursor(after, user_mui.shape[0])
     st = _lib.SCORE_TYPES.get(score_type)
     if st is None or st == _lib.SCORE_NONE:
         raise ValueError("Invalid method of aggregating matching score")  # model.py:136
@@ -335,7 +424,15 @@ def rank_topk(user_mui: Tensor, user_proj: Optional[Tensor], news: Tensor, topk:
     nws = int(lib.miner_rank_topk_workspace_bytes(U, topk)) if split else 0
     ws = torch.empty(nws, dtype=torch.uint8, device=dev) if nws else None
     with torch.cuda.device(dev):
-        if caps is not None:                                 # unsplit whatever the batch: no workspace
+        if cur is not None:                                  # every uncapped form, continued after the cursor
+            M = -1 if sub is None else sub.ids.numel()
+            rc = lib.miner_rank_topk_after(_stream(dev), dt, st, _ptr(mui), _ptr(proj), _ptr(tab), U, N, d, K, topk,
+                                           _ptr(excl), E, _ptr(ok), _ptr(sub.ids) if M > 0 else None, M,
+                                           _ptr(top_s), _ptr(top_i), _ptr(ws), nws,
+                                           None if pri is None else _ptr(pri.bias), 0 if pri is None else pri.G,
+                                           None if pri is None else _ptr(pri.group), None, 0,
+                                           _ptr(cur.scores), _ptr(cur.ids))
+        elif caps is not None:                               # unsplit whatever the batch: no workspace
             M = -1 if sub is None else sub.ids.numel()
             rc = lib.miner_rank_topk_capped(_stream(dev), dt, st, _ptr(mui), _ptr(proj), _ptr(tab), U, N, d, K, topk,
                                             _ptr(excl), E, _ptr(ok), _ptr(sub.ids) if M > 0 else None, M,
@@ -359,6 +456,41 @@ def rank_topk(user_mui: Tensor, user_proj: Optional[Tensor], news: Tensor, topk:
             rc = lib.miner_rank_topk_filtered(_stream(dev), dt, st, _ptr(mui), _ptr(proj), _ptr(tab), U, N, d, K,
                                               topk, _ptr(excl), E, _ptr(ok), _ptr(top_s), _ptr(top_i), _ptr(ws), nws)
     _lib.check(rc, "miner_rank_topk")
+    return top_s, top_i
+
+
+def rank_topk_deep(user_mui: Tensor, user_proj: Optional[Tensor], news: Tensor, topk: int, *, after=None,
+                   score_type: str = "weighted", exclude_ids: Optional[Tensor] = None,
+                   eligible: Optional[Tensor] = None, news_ids=None, news_bias=None,
+                   user_group: Optional[Tensor] = None, news_cluster=None, cluster_cap=None):
+    """rank_topk for any topk >= 1: (scores [U,topk] fp32, ids [U,topk] int32), best first, with the
+    (-inf, -1) tail — ceil(topk / 256) pages of rank_topk chained with page_cursor (the first from
+    ``after``, or from the top without it) and written side by side. Every page streams the table
+    once, so the cost is pages x the rank_topk step (profiles/rk_after_ab.txt), not one pass: a deep
+    list is paid for by its depth. The other arguments are rank_topk's; ``news_ids`` is canonicalised
+    once, the bitmap packed once and the prior checked once. No host synchronisation beyond
+    rank_topk's own argument checks. Per-cluster caps are not offered (no cursor under caps):
+    ``news_cluster`` / ``cluster_cap`` are named only to say so, anything but None raises ValueError."""
+    if news_cluster is not None or cluster_cap is not None:
+        raise ValueError("rank_topk_deep pages with cursors, and there is no cursor under news_cluster / cluster_cap")
+    if isinstance(topk, bool) or not isinstance(topk, int) or topk < 1:
+        raise ValueError("topk must be an int >= 1")
+    U, N = user_mui.shape[0], news.shape[0]
+    pri = _prior(news_bias, user_group, U, N)
+    cur = _cursor(after, U)
+    _require_device(user_mui, user_proj, news, exclude_ids, eligible)
+    ok = None if eligible is None else _eligible_words(eligible, N)
+    sub = None if news_ids is None else _news_id_list(news_ids, N)
+    dev = user_mui.device
+    top_s = torch.empty(U, topk, dtype=torch.float32, device=dev)
+    top_i = torch.empty(U, topk, dtype=torch.int32, device=dev)
+    for k0 in range(0, topk, MAX_TOPK):
+        k1 = min(topk, k0 + MAX_TOPK)
+        page = rank_topk(user_mui, user_proj, news, k1 - k0, score_type=score_type, exclude_ids=exclude_ids,
+                         eligible=ok, news_ids=sub, news_bias=pri, after=cur)
+        top_s[:, k0:k1], top_i[:, k0:k1] = page
+        if k1 < topk:
+            cur = _Cursor(*page_cursor(page))
     return top_s, top_i
 
 
@@ -733,7 +865,8 @@ def rank_corpus(news: Tensor, his_ids: Tensor, his_mask: Tensor, packed: Encoder
                 his_bias: Optional[Tensor] = None, score_type: str = "weighted", batch: int = 16384,
                 out: Optional[tuple] = None, exclude_history: bool = False, exclude_ids: Optional[Tensor] = None,
                 eligible: Optional[Tensor] = None, news_ids=None, news_bias=None,
-                user_group: Optional[Tensor] = None, news_cluster=None, cluster_cap: Optional[int] = None):
+                user_group: Optional[Tensor] = None, news_cluster=None, cluster_cap: Optional[int] = None,
+                after=None):
     """BASELINE config 5 on one GPU's share of the users: every user (his_ids [U,L] into the news
     table [N,d], his_mask [U,L]) encoded and ranked against the whole table, ``batch`` users per
     encode + rank pair so that the [batch,K,d] user vectors are all that is ever held (125,000 users
@@ -744,13 +877,16 @@ def rank_corpus(news: Tensor, his_ids: Tensor, his_mask: Tensor, packed: Encoder
     ``exclude_history`` keeps each user's own clicked news (the unmasked his_ids) out of its list,
     ``exclude_ids`` [U,E] further ids, together at most 256 per user; ``eligible`` and ``news_ids`` (rank only these table rows) as in
     rank_topk; ``news_bias`` / ``user_group`` [U] (a score prior, checked once and sliced per batch) too;
-    ``news_cluster`` / ``cluster_cap`` (per-cluster caps, checked and converted once) too."""
+    ``news_cluster`` / ``cluster_cap`` (per-cluster caps, checked and converted once) too; ``after``
+    (keyset cursors [U], checked once and sliced per batch; never together with the caps) too."""
     if batch <= 0:
         raise ValueError("batch must be positive")
     U = his_ids.shape[0]
     dev = news.device
+    _no_cursor_under_caps(after, news_cluster, cluster_cap)
     pri = _prior(news_bias, user_group, U, news.shape[0])
     caps = _caps(news_cluster, cluster_cap, news.shape[0])
+    cur = _cursor(after, U)
     _require_device(news, his_ids, his_mask, exclude_ids, eligible)
     excl = exclude_ids
     if excl is not None and (excl.dim() != 2 or excl.shape[0] != U):
@@ -771,7 +907,8 @@ def rank_corpus(news: Tensor, his_ids: Tensor, his_mask: Tensor, packed: Encoder
                                  his_bias=None if his_bias is None else his_bias[u0:u1], with_proj=with_proj)
         s, i = rank_topk(mui, proj, news, topk, score_type=score_type,
                          exclude_ids=None if excl is None else excl[u0:u1], eligible=ok, news_ids=sub,
-                         news_bias=None if pri is None else pri.users(u0, u1), news_cluster=caps)
+                         news_bias=None if pri is None else pri.users(u0, u1), news_cluster=caps,
+                         after=None if cur is None else cur.users(u0, u1))
         top_s[u0:u1] = s
         top_i[u0:u1] = i
     return top_s, top_i

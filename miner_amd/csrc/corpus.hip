@@ -463,6 +463,8 @@ struct RkParams {
   int G;
   const int32_t* clus;     // CAP: the cluster table [N] (< 0: in no cluster); a list holds at most cap news
   int cap;                 //      of one cluster
+  const float* aft_s;      // AFT: the keyset cursors [U] (NULL: none); user u's list holds only what ranks
+  const int32_t* aft_i;    //      strictly after (aft_s[u], aft_i[u])
 };
 
 // S > 1 (S = 8, grid = 256): the news steps are dealt to S slices (step st of slice s is news step
@@ -574,6 +576,18 @@ struct RkLds {
 // (rk_add_rn) on the finished score — before the threshold test, the key compare or the store, so
 // lists, counts and pair scores agree bit for bit with "scores + prior" in fp32. A compile-time
 // switch for the reason FLT is one: the unbiased instantiations are the same code as without it.
+// AFT: the cursor form (RkParams aft_s / aft_i; kRank, GEO 0, filtered — either filter may be null —,
+// split or unsplit, never CAP). A compile-time switch on the biased instantiation with the prior
+// tested at run time (the CAP pattern): as a run-time test on p.aft_s in the filtered instantiations
+// the filtered config-5 step without a cursor measured 81.27 against the parent's 80.39 ms, outside
+// the parent's own 0.74 ms spread (the two cursor words live in scalar registers across the step
+// loop), so every instantiation a call without a cursor launches is the code it was. A candidate
+// (score, n) of user u is kept only if better(aft_s[u], aft_i[u], score, n) — the ranked value (the biased sum under a prior) and the table id (ids[pos] in the subset form),
+// compared exactly as the threshold test compares, from the other side. So a cursor of +inf / -1 is
+// before every listable entry, -inf / 2^31 - 1 after all of them, a NaN cursor score lists nothing,
+// and a cursor that is no listable news is a position in the order like any other. The running
+// list, the staging, the merge and rk_merge never see an entry at or before the cursor: each slice
+// of the split form applies it, and split and unsplit agree bit for bit.
 // CAP: the capped form (RkParams clus / cap; kRank, unsplit, GEO 0, filtered). A user's list is the
 // greedy walk of its ranking that keeps an entry iff fewer than cap better entries of its cluster
 // were kept — a mergeable summary as the top-k is, so only the merge changes (below): the contraction,
@@ -592,8 +606,10 @@ __device__ __forceinline__ float rk_add_rn(float a, float b) {
 }
 
 template <class T, int NKT, int SCORE, int NCH = 0, int S = 1, int GEO = 0, int KC = 0, bool FLT = false,   // KC: K compile-time (0: run time)
-          bool SUB = false, int MODE = kRank, bool BIAS = false, bool CAP = false>
+          bool SUB = false, int MODE = kRank, bool BIAS = false, bool CAP = false, bool AFT = false>
 __global__ __launch_bounds__(kThreads) void rk_fused(RkParams p) {
+  static_assert(!AFT || (MODE == kRank && GEO == 0 && FLT && BIAS && !CAP), "the cursor form: filtered, on the biased form, uncapped");
+  constexpr bool kRtPrior = CAP || AFT;             // BIAS instantiations that test the prior at run time
   static_assert(!CAP || (MODE == kRank && S == 1 && GEO == 0 && FLT && BIAS), "the capped form: unsplit, filtered, on the biased form");
   static_assert(!SUB || (FLT && GEO == 0), "the subset form: a filtered form with one chunk in flight");
   static_assert(!BIAS || (GEO == 0 && (FLT || MODE == kCount)), "the biased forms: GEO 0, the ranking forms filtered");
@@ -940,7 +956,7 @@ __global__ __launch_bounds__(kThreads) void rk_fused(RkParams p) {
   // different rows); a user past U takes the last user's and a group outside [0, G) is clamped, so
   // no address leaves the table
   auto prior_row = [&](int t) -> const float* {
-    if constexpr (CAP) if (p.bias == nullptr) return nullptr;   // (the capped form without a prior)
+    if constexpr (kRtPrior) if (p.bias == nullptr) return nullptr;   // (the capped / cursor form without a prior)
     const int bu = min(MODE == kPair ? t : t * kUT + uu, p.U - 1);
     int g = 0;
     if (p.grp != nullptr) g = (int)rk_sload(reinterpret_cast<const uint32_t*>(p.grp) + bu);
@@ -961,7 +977,7 @@ __global__ __launch_bounds__(kThreads) void rk_fused(RkParams p) {
 #pragma unroll
     for (int nt = 0; nt < 2; ++nt) {
       const int n = SUB ? idn[nt] : news_step(s) * kNT + 64 * nsub + 32 * nt + (lane & 31);
-      pnx[nt] = (!CAP || p.bias != nullptr) && (SUB ? n >= 0 : n < N) ? prow[n] : 0.f;
+      pnx[nt] = (!kRtPrior || p.bias != nullptr) && (SUB ? n >= 0 : n < N) ? prow[n] : 0.f;
     }
   };
   if constexpr (BIAS) {                           // the first step's (complete behind the first chunk's wait)
@@ -989,6 +1005,17 @@ __global__ __launch_bounds__(kThreads) void rk_fused(RkParams p) {
         tg_h[threadIdx.x] = s == s ? rk_okey(s) : 0xffffffffu;
         tg_l[threadIdx.x] = s == s ? rk_ikey(id) : 0xffffffffu;
       }
+    }
+    // the cursor of this wave's user: two wave-uniform words through the scalar cache, once per
+    // (tile, user), held in scalar registers across the step loop (complete long before the first
+    // epilogue; never a vector load behind the row DMAs). A user past U reads the last user's and
+    // is never a candidate.
+    [[maybe_unused]] float aft_s = INFINITY;
+    [[maybe_unused]] int aft_i = -1;
+    if constexpr (AFT) {
+      const int au = min(ti * kUT + uu, p.U - 1);
+      aft_s = __uint_as_float(rk_sload(reinterpret_cast<const uint32_t*>(p.aft_s) + au));
+      aft_i = (int)rk_sload(reinterpret_cast<const uint32_t*>(p.aft_i) + au);
     }
     for (int sl = 0; sl < nsteps; ++sl) {
       const int st = news_step(sl);
@@ -1134,7 +1161,7 @@ __global__ __launch_bounds__(kThreads) void rk_fused(RkParams p) {
                 if (32 * kt + 16 * h + e < K) sm += acc[kt][nt][e];
             score = xor32_sum(sm) / (float)K;            // model.py:130-131
           }
-          if constexpr (BIAS) if (!CAP || p.bias != nullptr) score = rk_add_rn(score, pri[nt]);
+          if constexpr (BIAS) if (!kRtPrior || p.bias != nullptr) score = rk_add_rn(score, pri[nt]);
           if constexpr (MODE == kCount) {
             // Lane j holds the key of target j of user uu (a slot past T: the greatest key); lanes
             // 0..31 hold the scores of news n0 + lane. The 32 score keys are broadcast in turn
@@ -1174,6 +1201,11 @@ __global__ __launch_bounds__(kThreads) void rk_fused(RkParams p) {
           if constexpr (FLT) {
             if (bal) {
               const int n0 = st * kNT + 64 * nsub + 32 * nt;
+              if constexpr (AFT) {                         // the cursor: strictly after (aft_s, aft_i)
+                cand = cand && better(aft_s, aft_i, score, n);
+                bal = __ballot(cand);
+                if (!bal) continue;                        // (deep cursors: most half-waves end here)
+              }
               if (p.ok != nullptr) {
                 if constexpr (SUB) cand = cand && ((p.ok[n >> 5] >> (n & 31)) & 1u);   // per lane: ids are scattered
                 else cand = cand && ((p.ok[n0 >> 5] >> r) & 1u);
@@ -1475,22 +1507,22 @@ bool rk_split(const RkParams& prm) {
   return num_cus() == 256;
 }
 
-template <class T, int NKT, int S, int GEO, bool FLT, bool SUB = false, bool BIAS = false>
+template <class T, int NKT, int S, int GEO, bool FLT, bool SUB = false, bool BIAS = false, bool AFT = false>
 int rk_launch_geo(void* stream, const RkParams& prm, bool split) {
   // d = 768 in 16-bit (config 5): the chunk count compile-time
-  void (*kern)(RkParams) = split ? rk_fused<T, NKT, S, 0, kSplit, GEO, 0, FLT, SUB, kRank, BIAS>
-                                 : rk_fused<T, NKT, S, 0, 1, GEO, 0, FLT, SUB, kRank, BIAS>;
+  void (*kern)(RkParams) = split ? rk_fused<T, NKT, S, 0, kSplit, GEO, 0, FLT, SUB, kRank, BIAS, false, AFT>
+                                 : rk_fused<T, NKT, S, 0, 1, GEO, 0, FLT, SUB, kRank, BIAS, false, AFT>;
   if constexpr (sizeof(T) == 2) {
     // config 5's d = 768 and K = 64 compile-time (the masked interest loops of the epilogue compile
     // away; the top-k equals the oracle's at the 16-bit bar, tests/test_gpu_corpus.py)
     constexpr int kN768 = 768 * 2 / kRB<GEO>;
     if (prm.d == 768) {
       if (NKT == 2 && prm.K == 64)
-        kern = split ? rk_fused<T, NKT, S, kN768, kSplit, GEO, 64, FLT, SUB, kRank, BIAS>
-                     : rk_fused<T, NKT, S, kN768, 1, GEO, 64, FLT, SUB, kRank, BIAS>;
+        kern = split ? rk_fused<T, NKT, S, kN768, kSplit, GEO, 64, FLT, SUB, kRank, BIAS, false, AFT>
+                     : rk_fused<T, NKT, S, kN768, 1, GEO, 64, FLT, SUB, kRank, BIAS, false, AFT>;
       else
-        kern = split ? rk_fused<T, NKT, S, kN768, kSplit, GEO, 0, FLT, SUB, kRank, BIAS>
-                     : rk_fused<T, NKT, S, kN768, 1, GEO, 0, FLT, SUB, kRank, BIAS>;
+        kern = split ? rk_fused<T, NKT, S, kN768, kSplit, GEO, 0, FLT, SUB, kRank, BIAS, false, AFT>
+                     : rk_fused<T, NKT, S, kN768, 1, GEO, 0, FLT, SUB, kRank, BIAS, false, AFT>;
     }
   }
   constexpr int NR = S == MINER_SCORE_WEIGHTED ? 2 * NKT : NKT;
@@ -1542,6 +1574,11 @@ int rk_launch(void* stream, const RkParams& prm) {
   if (prm.clus != nullptr)
     return prm.ids != nullptr ? rk_launch_cap<T, NKT, S, true>(stream, prm) : rk_launch_cap<T, NKT, S, false>(stream, prm);
   const bool split = rk_split(prm);
+  // the cursor form: one instantiation per shape (table / subset, split or not), on the biased form
+  // with the prior tested at run time and either filter null or not
+  if (prm.aft_s != nullptr)
+    return prm.ids != nullptr ? rk_launch_geo<T, NKT, S, 0, true, true, true, true>(stream, prm, split)
+                              : rk_launch_geo<T, NKT, S, 0, true, false, true, true>(stream, prm, split);
   const bool flt = prm.ok != nullptr || prm.E > 0;     // the filtered instantiation only when asked for
   // the subset form: one instantiation per shape, the filtered one (either filter may be null),
   // with the chunk count and K chosen as for the table forms
@@ -1655,7 +1692,8 @@ int rk_run(void* stream, int dtype, int score_type, const void* user_mui, const 
            int N, int d, int K, int topk, const int32_t* exclude_ids, int E, const uint32_t* news_ok, bool subset,
            const int32_t* news_ids, int M, float* top_scores, int32_t* top_ids, void* workspace, size_t workspace_bytes,
            const float* news_bias = nullptr, int G = 0, const int32_t* user_group = nullptr,
-           const int32_t* news_cluster = nullptr, int cap = 0) {
+           const int32_t* news_cluster = nullptr, int cap = 0, const float* after_scores = nullptr,
+           const int32_t* after_ids = nullptr) {
   const int ck = check_dims(dtype, d, 1, K);
   if (ck != MINER_OK) return ck;
   if (score_type < MINER_SCORE_WEIGHTED || score_type > MINER_SCORE_MEAN) return MINER_EINVAL;
@@ -1676,6 +1714,11 @@ int rk_run(void* stream, int dtype, int score_type, const void* user_mui, const 
   const int cc = cap_check(news_cluster, cap);
   if (cc != MINER_OK) return cc;
   if (!aligned4(news_cluster)) return MINER_EALIGN;
+  // the cursor: both words or neither, never with caps (a capped walk also needs the earlier pages'
+  // per-cluster counts, which a (score, id) pair does not carry)
+  if ((after_scores == nullptr) != (after_ids == nullptr)) return MINER_EINVAL;
+  if (after_scores != nullptr && news_cluster != nullptr) return MINER_EINVAL;
+  if (!aligned4(after_scores) || !aligned4(after_ids)) return MINER_EALIGN;
   if (U == 0) return MINER_OK;
   RkParams prm{};
   if (!aligned16(workspace)) return MINER_EALIGN;
@@ -1697,6 +1740,7 @@ int rk_run(void* stream, int dtype, int score_type, const void* user_mui, const 
   prm.ids = subset ? news_ids : nullptr; prm.M = subset ? M : 0;
   prm.bias = news_bias; prm.grp = news_bias ? user_group : nullptr; prm.G = news_bias ? G : 0;
   prm.clus = news_cluster; prm.cap = news_cluster ? cap : 0;
+  prm.aft_s = after_scores; prm.aft_i = after_ids;
   if (dtype == MINER_DTYPE_BF16) return rk_dispatch<__bf16>(stream, prm);
   if (dtype == MINER_DTYPE_F16) return rk_dispatch<_Float16>(stream, prm);
   return rk_dispatch<float>(stream, prm);
@@ -1878,6 +1922,18 @@ int miner_rank_topk_capped(void* stream, int dtype, int score_type, const void* 
   return rk_run(stream, dtype, score_type, user_mui, user_proj, news, U, N, d, K, topk, exclude_ids, E, news_ok, !table,
                 table ? nullptr : news_ids, table ? 0 : M, top_scores, top_ids, workspace, workspace_bytes, news_bias, G,
                 user_group, news_cluster, cap);
+}
+
+int miner_rank_topk_after(void* stream, int dtype, int score_type, const void* user_mui, const void* user_proj,
+                          const void* news, int U, int N, int d, int K, int topk, const int32_t* exclude_ids, int E,
+                          const uint32_t* news_ok, const int32_t* news_ids, int M, float* top_scores, int32_t* top_ids,
+                          void* workspace, size_t workspace_bytes, const float* news_bias, int G,
+                          const int32_t* user_group, const int32_t* news_cluster, int cap, const float* after_scores,
+                          const int32_t* after_ids) {
+  const bool table = news_ids == nullptr && M < 0;     // the whole table: the filtered form
+  return rk_run(stream, dtype, score_type, user_mui, user_proj, news, U, N, d, K, topk, exclude_ids, E, news_ok, !table,
+                table ? nullptr : news_ids, table ? 0 : M, top_scores, top_ids, workspace, workspace_bytes, news_bias, G,
+                user_group, news_cluster, cap, after_scores, after_ids);
 }
 
 int miner_topk_merge(void* stream, const float* a_scores, const int32_t* a_ids, int ka, const float* b_scores,
