@@ -223,6 +223,11 @@ def _prior(news_bias, user_group, U: int, N: int) -> Optional[_Prior]:
     return _Prior(news_bias.reshape(G, N).contiguous(), _contig(user_group, torch.int32))
 
 
+def _prior_args(pri: Optional[_Prior]):
+    """(news_bias, G, user_group) of the C entries: a checked prior's, or NULL / 0 / NULL without one."""
+    return (None, 0, None) if pri is None else (_ptr(pri.bias), pri.G, _ptr(pri.group))
+
+
 @dataclasses.dataclass
 class _Caps:
     """Checked per-cluster caps: cluster int32 [N] contiguous on the device, cap in [1, MAX_TOPK]."""
@@ -383,21 +388,9 @@ def rank_topk(user_mui: Tensor, user_proj: Optional[Tensor], news: Tensor, topk:
     pri = _prior(news_bias, user_group, user_mui.shape[0], news.shape[0])
     caps = _caps(news_cluster, cluster_cap, news.shape[0])
     cur = _cursor(after, user_mui.shape[0])
-    st = _lib.SCORE_TYPES.get(score_type)
-    if st is None or st == _lib.SCORE_NONE:
-        raise ValueError("Invalid method of aggregating matching score")  # model.py:136
-    _require_device(user_mui, user_proj, news)
-    dtype = user_mui.dtype
-    dt = _code(dtype)
-    mui = _contig(user_mui, dtype)
-    proj = _contig(user_proj, dtype) if st == _lib.SCORE_WEIGHTED else None
-    if st == _lib.SCORE_WEIGHTED and proj is None:
-        raise ValueError("score_type 'weighted' needs user_proj")
-    tab = _contig(news, dtype)
+    st, dt, mui, proj, tab = _rank_operands(user_mui, user_proj, news, score_type)
     U, K, d = mui.shape
     N = tab.shape[0]
-    if tab.shape[1] != d or (proj is not None and proj.shape != mui.shape):
-        raise ValueError("shape mismatch between user vectors and the news table")
     if not 1 <= topk <= MAX_TOPK:
         raise ValueError(f"topk must be in [1, {MAX_TOPK}]")
     _require_device(exclude_ids, eligible)
@@ -423,38 +416,14 @@ def rank_topk(user_mui: Tensor, user_proj: Optional[Tensor], news: Tensor, topk:
     split = split and caps is None
     nws = int(lib.miner_rank_topk_workspace_bytes(U, topk)) if split else 0
     ws = torch.empty(nws, dtype=torch.uint8, device=dev) if nws else None
+    M = -1 if sub is None else sub.ids.numel()               # -1 with no list: the whole table
     with torch.cuda.device(dev):
-        if cur is not None:                                  # every uncapped form, continued after the cursor
-            M = -1 if sub is None else sub.ids.numel()
-            rc = lib.miner_rank_topk_after(_stream(dev), dt, st, _ptr(mui), _ptr(proj), _ptr(tab), U, N, d, K, topk,
-                                           _ptr(excl), E, _ptr(ok), _ptr(sub.ids) if M > 0 else None, M,
-                                           _ptr(top_s), _ptr(top_i), _ptr(ws), nws,
-                                           None if pri is None else _ptr(pri.bias), 0 if pri is None else pri.G,
-                                           None if pri is None else _ptr(pri.group), None, 0,
-                                           _ptr(cur.scores), _ptr(cur.ids))
-        elif caps is not None:                               # unsplit whatever the batch: no workspace
-            M = -1 if sub is None else sub.ids.numel()
-            rc = lib.miner_rank_topk_capped(_stream(dev), dt, st, _ptr(mui), _ptr(proj), _ptr(tab), U, N, d, K, topk,
-                                            _ptr(excl), E, _ptr(ok), _ptr(sub.ids) if M > 0 else None, M,
-                                            _ptr(top_s), _ptr(top_i), None, 0,
-                                            None if pri is None else _ptr(pri.bias), 0 if pri is None else pri.G,
-                                            None if pri is None else _ptr(pri.group), _ptr(caps.cluster), caps.cap)
-        elif pri is not None:
-            M = -1 if sub is None else sub.ids.numel()       # -1 with no list: the whole table
-            rc = lib.miner_rank_topk_biased(_stream(dev), dt, st, _ptr(mui), _ptr(proj), _ptr(tab), U, N, d, K, topk,
-                                            _ptr(excl), E, _ptr(ok), _ptr(sub.ids) if M > 0 else None, M,
-                                            _ptr(top_s), _ptr(top_i), _ptr(ws), nws, _ptr(pri.bias), pri.G,
-                                            _ptr(pri.group))
-        elif sub is not None:
-            rc = lib.miner_rank_topk_subset(_stream(dev), dt, st, _ptr(mui), _ptr(proj), _ptr(tab), U, N, d, K, topk,
-                                            _ptr(excl), E, _ptr(ok), _ptr(sub.ids) if sub.ids.numel() else None,
-                                            sub.ids.numel(), _ptr(top_s), _ptr(top_i), _ptr(ws), nws)
-        elif excl is None and ok is None:
-            rc = lib.miner_rank_topk_ws(_stream(dev), dt, st, _ptr(mui), _ptr(proj), _ptr(tab), U, N, d, K, topk,
-                                        _ptr(top_s), _ptr(top_i), _ptr(ws), nws)
-        else:
-            rc = lib.miner_rank_topk_filtered(_stream(dev), dt, st, _ptr(mui), _ptr(proj), _ptr(tab), U, N, d, K,
-                                              topk, _ptr(excl), E, _ptr(ok), _ptr(top_s), _ptr(top_i), _ptr(ws), nws)
+        # the widest entry; what the call does not use is NULL and launches the narrower entry's kernel
+        rc = lib.miner_rank_topk_after(_stream(dev), dt, st, _ptr(mui), _ptr(proj), _ptr(tab), U, N, d, K, topk,
+                                       _ptr(excl), E, _ptr(ok), _ptr(sub.ids) if M > 0 else None, M, _ptr(top_s),
+                                       _ptr(top_i), _ptr(ws), nws, *_prior_args(pri),
+                                       None if caps is None else _ptr(caps.cluster), 0 if caps is None else caps.cap,
+                                       None if cur is None else _ptr(cur.scores), None if cur is None else _ptr(cur.ids))
     _lib.check(rc, "miner_rank_topk")
     return top_s, top_i
 
@@ -545,15 +514,11 @@ def merge_topk(a, b, topk: Optional[int] = None, *, eligible: Optional[Tensor] =
     out_s = torch.empty(U, topk, dtype=torch.float32, device=dev)
     out_i = torch.empty(U, topk, dtype=torch.int32, device=dev)
     with torch.cuda.device(dev):
-        if caps is not None:
-            rc = _lib.lib().miner_topk_merge_capped(_stream(dev), _ptr(a_s) if ka else None, _ptr(a_i) if ka else None,
-                                                    ka, _ptr(b_s) if kb else None, _ptr(b_i) if kb else None, kb, U,
-                                                    topk, _ptr(ok), N, _ptr(out_s), _ptr(out_i), _ptr(caps.cluster),
-                                                    caps.cluster.shape[0], caps.cap)
-        else:
-            rc = _lib.lib().miner_topk_merge(_stream(dev), _ptr(a_s) if ka else None, _ptr(a_i) if ka else None, ka,
-                                             _ptr(b_s) if kb else None, _ptr(b_i) if kb else None, kb, U, topk, _ptr(ok),
-                                             N, _ptr(out_s), _ptr(out_i))
+        rc = _lib.lib().miner_topk_merge_capped(_stream(dev), _ptr(a_s) if ka else None, _ptr(a_i) if ka else None, ka,
+                                                _ptr(b_s) if kb else None, _ptr(b_i) if kb else None, kb, U, topk,
+                                                _ptr(ok), N, _ptr(out_s), _ptr(out_i),
+                                                None if caps is None else _ptr(caps.cluster),
+                                                0 if caps is None else caps.cluster.shape[0], 0 if caps is None else caps.cap)
     _lib.check(rc, "miner_topk_merge")
     return out_s, out_i
 
@@ -654,13 +619,8 @@ def _score_pairs(st, dt, mui, proj, tab, ids64: Tensor, pri: Optional[_Prior] = 
         return out
     ids = ids64.to(torch.int32).contiguous()
     with torch.cuda.device(mui.device):
-        if pri is not None:
-            rc = _lib.lib().miner_score_pairs_biased(_stream(mui.device), dt, st, _ptr(mui), _ptr(proj), _ptr(tab), U,
-                                                     tab.shape[0], d, K, _ptr(ids), C, _ptr(out), _ptr(pri.bias),
-                                                     pri.G, _ptr(pri.group))
-        else:
-            rc = _lib.lib().miner_score_pairs(_stream(mui.device), dt, st, _ptr(mui), _ptr(proj), _ptr(tab), U,
-                                              tab.shape[0], d, K, _ptr(ids), C, _ptr(out))
+        rc = _lib.lib().miner_score_pairs_biased(_stream(mui.device), dt, st, _ptr(mui), _ptr(proj), _ptr(tab), U,
+                                                 tab.shape[0], d, K, _ptr(ids), C, _ptr(out), *_prior_args(pri))
     _lib.check(rc, "miner_score_pairs")
     return out
 
@@ -711,13 +671,8 @@ def _rank_of(user_mui, user_proj, news, target_ids, score_type, exclude_ids, eli
     if U:
         tid32 = tid.to(torch.int32).contiguous()
         with torch.cuda.device(dev):
-            if pri is not None:
-                rc = _lib.lib().miner_rank_count_biased(_stream(dev), dt, st, _ptr(mui), _ptr(proj), _ptr(tab), U, N, d,
-                                                        K, _ptr(tgt_s), _ptr(tid32), T, _ptr(ok), _ptr(counts),
-                                                        _ptr(pri.bias), pri.G, _ptr(pri.group))
-            else:
-                rc = _lib.lib().miner_rank_count(_stream(dev), dt, st, _ptr(mui), _ptr(proj), _ptr(tab), U, N, d, K,
-                                                 _ptr(tgt_s), _ptr(tid32), T, _ptr(ok), _ptr(counts))
+            rc = _lib.lib().miner_rank_count_biased(_stream(dev), dt, st, _ptr(mui), _ptr(proj), _ptr(tab), U, N, d, K,
+                                                    _ptr(tgt_s), _ptr(tid32), T, _ptr(ok), _ptr(counts), *_prior_args(pri))
         _lib.check(rc, "miner_rank_count")
     appears = (tid >= 0) & ~torch.isnan(tgt_s)
     if ok is not None:
@@ -819,6 +774,21 @@ def rescore_topk(lists, user_mui: Tensor, user_proj: Optional[Tensor], news: Ten
     return merge_topk(empty, (fresh, ids), ids.shape[1], eligible=eligible)
 
 
+def _exclusions(exclude_ids: Optional[Tensor], exclude_history: bool, his_ids: Tensor, his_mask: Tensor):
+    """The exclusion matrix of rank_corpus / evaluate_corpus: ``exclude_ids`` [U, E], behind each
+    user's own history when ``exclude_history``; None when there is neither."""
+    U = his_ids.shape[0]
+    excl = exclude_ids
+    if excl is not None and (excl.dim() != 2 or excl.shape[0] != U):
+        raise ValueError(f"exclude_ids must be [{U}, E]")
+    if exclude_history:
+        seen = torch.where(his_mask.to(torch.bool), his_ids, -1).to(torch.int32)   # padded slots exclude nothing
+        excl = seen if excl is None else torch.cat([seen, excl.to(torch.int32)], dim=1)
+    if excl is not None and excl.shape[1] > MAX_L:
+        raise ValueError(f"{excl.shape[1]} excluded ids per user, more than {MAX_L}")
+    return excl
+
+
 def evaluate_corpus(news: Tensor, his_ids: Tensor, his_mask: Tensor, packed: EncoderWeights, target_ids: Tensor, *,
                     ks=(5, 10), batch: int = 16384, exclude_history: bool = True,
                     exclude_ids: Optional[Tensor] = None, eligible: Optional[Tensor] = None,
@@ -837,14 +807,7 @@ def evaluate_corpus(news: Tensor, his_ids: Tensor, his_mask: Tensor, packed: Enc
     dev = news.device
     pri = _prior(news_bias, user_group, U, news.shape[0])
     _require_device(news, his_ids, his_mask, target_ids, exclude_ids, eligible)
-    excl = exclude_ids
-    if excl is not None and (excl.dim() != 2 or excl.shape[0] != U):
-        raise ValueError(f"exclude_ids must be [{U}, E]")
-    if exclude_history:
-        seen = torch.where(his_mask.to(torch.bool), his_ids, -1).to(torch.int32)   # padded slots exclude nothing
-        excl = seen if excl is None else torch.cat([seen, excl.to(torch.int32)], dim=1)
-    if excl is not None and excl.shape[1] > MAX_L:
-        raise ValueError(f"{excl.shape[1]} excluded ids per user, more than {MAX_L}")
+    excl = _exclusions(exclude_ids, exclude_history, his_ids, his_mask)
     if target_ids.dim() != 2 or target_ids.shape[0] != U:
         raise ValueError(f"target_ids must be [{U}, T]")
     ok = None if eligible is None else _eligible_words(eligible, news.shape[0])   # packed once
@@ -888,14 +851,7 @@ def rank_corpus(news: Tensor, his_ids: Tensor, his_mask: Tensor, packed: Encoder
     caps = _caps(news_cluster, cluster_cap, news.shape[0])
     cur = _cursor(after, U)
     _require_device(news, his_ids, his_mask, exclude_ids, eligible)
-    excl = exclude_ids
-    if excl is not None and (excl.dim() != 2 or excl.shape[0] != U):
-        raise ValueError(f"exclude_ids must be [{U}, E]")
-    if exclude_history:
-        seen = torch.where(his_mask.to(torch.bool), his_ids, -1).to(torch.int32)   # padded slots exclude nothing
-        excl = seen if excl is None else torch.cat([seen, excl.to(torch.int32)], dim=1)
-    if excl is not None and excl.shape[1] > MAX_L:
-        raise ValueError(f"{excl.shape[1]} excluded ids per user, more than {MAX_L}")
+    excl = _exclusions(exclude_ids, exclude_history, his_ids, his_mask)
     ok = None if eligible is None else _eligible_words(eligible, news.shape[0])   # packed once
     sub = None if news_ids is None else _news_id_list(news_ids, news.shape[0])    # canonicalised once
     top_s, top_i = out if out is not None else (torch.empty(U, topk, dtype=torch.float32, device=dev),

@@ -26,6 +26,7 @@
 #include <stdlib.h>
 #include <stdint.h>
 #include <math.h>
+#include <utility>
 
 #include "../../include/miner_corpus.h"
 #include "cdna4_common.h"
@@ -605,15 +606,32 @@ __device__ __forceinline__ float rk_add_rn(float a, float b) {
   return __fadd_rn(a, b);
 }
 
-template <class T, int NKT, int SCORE, int NCH = 0, int S = 1, int GEO = 0, int KC = 0, bool FLT = false,   // KC: K compile-time (0: run time)
-          bool SUB = false, int MODE = kRank, bool BIAS = false, bool CAP = false, bool AFT = false>
-__global__ __launch_bounds__(kThreads) void rk_fused(RkParams p) {
+// A form: every compile-time switch of rk_fused but T / NKT / SCORE, in one word — the switches
+// above as named bits, kCount / kPair for MODE (neither: kRank), kFSplit for S = kSplit, and the
+// shape bits of the launcher (kFD768: NCH = 768 · 2 / RB, kFK64: KC = 64; 0 is "at run time").
+constexpr unsigned kFFlt = 1, kFSub = 2, kFBias = 4, kFCap = 8, kFAft = 16, kFGeo1 = 32, kFSplit = 64, kFCount = 128,
+                   kFPair = 256, kFD768 = 512, kFK64 = 1024;
+template <unsigned F>
+struct RkForm {
+  static constexpr bool FLT = F & kFFlt, SUB = F & kFSub, BIAS = F & kFBias, CAP = F & kFCap, AFT = F & kFAft;
+  static constexpr int MODE = F & kFCount ? kCount : F & kFPair ? kPair : kRank;
+  static constexpr int S = F & kFSplit ? kSplit : 1, GEO = F & kFGeo1 ? 1 : 0;
+  static constexpr int NCH = F & kFD768 ? 768 * 2 / kRB<GEO> : 0, KC = F & kFK64 ? 64 : 0;   // KC: K compile-time (0: run time)
+  static_assert(F < 2 * kFK64 && (F & (kFCount | kFPair)) != (kFCount | kFPair) && (!(F & kFK64) || (F & kFD768)), "a form");
   static_assert(!AFT || (MODE == kRank && GEO == 0 && FLT && BIAS && !CAP), "the cursor form: filtered, on the biased form, uncapped");
-  constexpr bool kRtPrior = CAP || AFT;             // BIAS instantiations that test the prior at run time
   static_assert(!CAP || (MODE == kRank && S == 1 && GEO == 0 && FLT && BIAS), "the capped form: unsplit, filtered, on the biased form");
   static_assert(!SUB || (FLT && GEO == 0), "the subset form: a filtered form with one chunk in flight");
   static_assert(!BIAS || (GEO == 0 && (FLT || MODE == kCount)), "the biased forms: GEO 0, the ranking forms filtered");
   static_assert(MODE == kRank || (S == 1 && GEO == 0 && SUB == (MODE == kPair)), "counting and pair forms: unsplit, GEO 0");
+};
+
+template <class T, int NKT, int SCORE, unsigned F>
+__global__ __launch_bounds__(kThreads) void rk_fused(RkParams p) {
+  using Fm = RkForm<F>;
+  constexpr int NCH = Fm::NCH, S = Fm::S, GEO = Fm::GEO, KC = Fm::KC, MODE = Fm::MODE;
+  constexpr bool FLT = Fm::FLT, SUB = Fm::SUB, BIAS = Fm::BIAS, CAP = Fm::CAP, AFT = Fm::AFT;
+  static_assert((NCH == 0 || sizeof(T) == 2) && (KC == 0 || NKT == 2), "the compile-time shape: 16-bit, K = 64 on two interest tiles");
+  constexpr bool kRtPrior = CAP || AFT;             // BIAS instantiations that test the prior at run time
   static_assert(kMaxT == 64 && kUT * kMaxT * 8 <= kUT * kMaxTopk * 8 && kUT * 4 * kMaxT * 4 <= 2 * kUT * kNT * 8,
                 "one target per lane; the targets in the list area, the partial counts in the staging area");
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -1507,30 +1525,71 @@ bool rk_split(const RkParams& prm) {
   return num_cus() == 256;
 }
 
-template <class T, int NKT, int S, int GEO, bool FLT, bool SUB = false, bool BIAS = false, bool AFT = false>
-int rk_launch_geo(void* stream, const RkParams& prm, bool split) {
-  // d = 768 in 16-bit (config 5): the chunk count compile-time
-  void (*kern)(RkParams) = split ? rk_fused<T, NKT, S, 0, kSplit, GEO, 0, FLT, SUB, kRank, BIAS, false, AFT>
-                                 : rk_fused<T, NKT, S, 0, 1, GEO, 0, FLT, SUB, kRank, BIAS, false, AFT>;
+// The forms the library launches: the table below, and rk_form, the one rule that maps a call to
+// its entry. Every feature is a compile-time switch so that a call without it launches the code it
+// launched before the feature existed (the measured costs of run-time tests: the switches above).
+constexpr unsigned kFSubset = kFFlt | kFSub;       // the subset form: filtered (either filter may be null)
+constexpr unsigned kFBiased = kFFlt | kFBias;      // the biased ranking forms: filtered (as the subset form), GEO 0
+constexpr unsigned kFCursor = kFBiased | kFAft;    // the cursor form: on the biased form, the prior tested at run time
+constexpr unsigned kFCapped = kFBiased | kFCap;    // the capped form: on the biased form likewise, unsplit
+constexpr unsigned kFPairs = kFPair | kFSubset;    // the pair form gathers: SUB (and so FLT)
+constexpr unsigned kRkForms[] = {
+    0, kFFlt, kFSubset, kFBiased, kFBiased | kFSub, kFCursor, kFCursor | kFSub,
+    kFSplit, kFSplit | kFFlt, kFSplit | kFSubset, kFSplit | kFBiased, kFSplit | kFBiased | kFSub, kFSplit | kFCursor,
+    kFSplit | kFCursor | kFSub,
+    kFCapped, kFCapped | kFSub, kFCount, kFCount | kFBias, kFPairs, kFPairs | kFBias,
+#ifdef MINER_RK_GEO1
+    kFGeo1, kFGeo1 | kFFlt, kFGeo1 | kFSplit, kFGeo1 | kFSplit | kFFlt,
+#endif
+};
+
+unsigned rk_form(const RkParams& prm, int mode, [[maybe_unused]] int dtype) {
+  // the counting and pair forms: unsplit, GEO 0; the biased instantiation only when a prior table
+  // was given (the unbiased calls launch what they did)
+  if (mode == kCount) return kFCount | (prm.bias != nullptr ? kFBias : 0);
+  if (mode == kPair) return kFPairs | (prm.bias != nullptr ? kFBias : 0);
+  // the id list: one instantiation per shape of every form below, table or subset
+  const unsigned sub = prm.ids != nullptr ? kFSub : 0;
+  // the capped form — two kernels per shape (table / subset), not four. A workspace is never written.
+  if (prm.clus != nullptr) return kFCapped | sub;
+  const unsigned split = rk_split(prm) ? kFSplit : 0;
+  if (prm.aft_s != nullptr) return kFCursor | sub | split;
+  if (prm.bias != nullptr) return kFBiased | sub | split;
+  if (sub) return kFSubset | split;
+  const unsigned flt = prm.ok != nullptr || prm.E > 0 ? kFFlt : 0;     // the filtered instantiation only when asked for
+  // (GEO 1 — 64-byte rows through a 4-stage ring, three chunks in flight instead of one — measured
+  // slower: 95.9 vs 89.7 ms per config-5 step, twice the barriers for no gain in the gather rate;
+  // diagnostic builds with -DMINER_RK_GEO1 launch it, in 16-bit with at least two row tiles per user)
+#ifdef MINER_RK_GEO1
+  if (dtype != MINER_DTYPE_F32 && (prm.K > 32 || prm.score_type == MINER_SCORE_WEIGHTED)) return kFGeo1 | flt | split;
+#endif
+  return flt | split;
+}
+
+// the one launcher: form F of the table with the compile-time shape added — in 16-bit config 5's
+// d = 768 as the chunk count and, on two interest tiles, its K = 64 (the masked interest loops of
+// the epilogue compile away; the top-k equals the oracle's at the 16-bit bar, tests/test_gpu_corpus.py).
+// Every form takes its shape by this rule, so a pair's score has the bits of the ranking form that
+// the same shape launches.
+template <class T, int NKT, int SCORE, unsigned F0>
+int rk_launch(void* stream, const RkParams& prm) {
+  constexpr int NR = SCORE == MINER_SCORE_WEIGHTED ? 2 * NKT : NKT;
+  constexpr unsigned F = sizeof(T) == 2 && NR >= 2 ? F0 : F0 & ~kFGeo1;   // (rk_form asks for GEO 1 nowhere else)
+  using Fm = RkForm<F>;
+  void (*kern)(RkParams) = rk_fused<T, NKT, SCORE, F>;
   if constexpr (sizeof(T) == 2) {
-    // config 5's d = 768 and K = 64 compile-time (the masked interest loops of the epilogue compile
-    // away; the top-k equals the oracle's at the 16-bit bar, tests/test_gpu_corpus.py)
-    constexpr int kN768 = 768 * 2 / kRB<GEO>;
     if (prm.d == 768) {
-      if (NKT == 2 && prm.K == 64)
-        kern = split ? rk_fused<T, NKT, S, kN768, kSplit, GEO, 64, FLT, SUB, kRank, BIAS, false, AFT>
-                     : rk_fused<T, NKT, S, kN768, 1, GEO, 64, FLT, SUB, kRank, BIAS, false, AFT>;
-      else
-        kern = split ? rk_fused<T, NKT, S, kN768, kSplit, GEO, 0, FLT, SUB, kRank, BIAS, false, AFT>
-                     : rk_fused<T, NKT, S, kN768, 1, GEO, 0, FLT, SUB, kRank, BIAS, false, AFT>;
+      kern = rk_fused<T, NKT, SCORE, F | kFD768>;
+      if constexpr (NKT == 2)
+        if (prm.K == 64) kern = rk_fused<T, NKT, SCORE, F | kFD768 | kFK64>;
     }
   }
-  constexpr int NR = S == MINER_SCORE_WEIGHTED ? 2 * NKT : NKT;
-  const int lds = RkLds<NR, GEO, FLT>::kTotal;
-  static_assert(RkLds<NR, GEO, true>::kTotal <= 160 * 1024, "ranker LDS (with the exclusion lists)");
+  constexpr int lds = RkLds<NR, Fm::GEO, Fm::FLT, Fm::CAP>::kTotal;
+  static_assert(lds <= 160 * 1024, "ranker LDS (with the exclusion lists and the cluster ids of the form)");
   hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
   if (e != hipSuccess) return (int)e;
-  const int ntiles = (prm.U + kUT - 1) / kUT;
+  constexpr bool split = Fm::S > 1;
+  const int ntiles = Fm::MODE == kPair ? prm.U : (prm.U + kUT - 1) / kUT;   // pair form: a tile is one user
   int grid = num_cus();
   if (!split && grid > ntiles) grid = ntiles;
   hipStream_t s = static_cast<hipStream_t>(stream);
@@ -1543,118 +1602,46 @@ int rk_launch_geo(void* stream, const RkParams& prm, bool split) {
   return e == hipSuccess ? MINER_OK : (int)e;
 }
 
-// the capped form (CAP): unsplit, filtered (either filter may be null), on the biased instantiation
-// with the prior tested at run time — two kernels per shape (table / subset), not four; the chunk
-// count and K compile-time by rk_launch_geo's rule. A workspace is never written.
-template <class T, int NKT, int S, bool SUB>
-int rk_launch_cap(void* stream, const RkParams& prm) {
-  void (*kern)(RkParams) = rk_fused<T, NKT, S, 0, 1, 0, 0, true, SUB, kRank, true, true>;
-  if constexpr (sizeof(T) == 2) {
-    constexpr int kN768 = 768 * 2 / kRB<0>;
-    if (prm.d == 768) {
-      kern = rk_fused<T, NKT, S, kN768, 1, 0, 0, true, SUB, kRank, true, true>;
-      if constexpr (NKT == 2)
-        if (prm.K == 64) kern = rk_fused<T, NKT, S, kN768, 1, 0, 64, true, SUB, kRank, true, true>;
-    }
-  }
-  constexpr int NR = S == MINER_SCORE_WEIGHTED ? 2 * NKT : NKT;
-  const int lds = RkLds<NR, 0, true, true>::kTotal;
-  static_assert(RkLds<NR, 0, true, true>::kTotal <= 160 * 1024, "ranker LDS (the capped form: exclusion lists and cluster ids)");
-  hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-  if (e != hipSuccess) return (int)e;
-  const int ntiles = (prm.U + kUT - 1) / kUT;
-  const int grid = num_cus() < ntiles ? num_cus() : ntiles;
-  hipLaunchKernelGGL(kern, dim3(grid), dim3(kThreads), lds, static_cast<hipStream_t>(stream), prm);
-  e = hipGetLastError();
-  return e == hipSuccess ? MINER_OK : (int)e;
+// the one ladder, for every mode: dtype, K <= 32 (one interest tile), score type, then the table
+template <class T, int NKT, int SCORE, size_t... I>
+int rk_pick(void* stream, const RkParams& prm, unsigned form, std::index_sequence<I...>) {
+  int rc = MINER_EINVAL;
+  (void)((form == kRkForms[I] && ((rc = rk_launch<T, NKT, SCORE, kRkForms[I]>(stream, prm)), true)) || ...);
+  return rc;
+}
+template <class T, int NKT>
+int rk_by_score(void* stream, const RkParams& prm, unsigned form) {
+  constexpr std::make_index_sequence<sizeof(kRkForms) / sizeof(kRkForms[0])> all{};
+  if (prm.score_type == MINER_SCORE_WEIGHTED) return rk_pick<T, NKT, MINER_SCORE_WEIGHTED>(stream, prm, form, all);
+  if (prm.score_type == MINER_SCORE_MAX) return rk_pick<T, NKT, MINER_SCORE_MAX>(stream, prm, form, all);
+  return rk_pick<T, NKT, MINER_SCORE_MEAN>(stream, prm, form, all);
+}
+template <class T>
+int rk_by_k(void* stream, const RkParams& prm, unsigned form) {
+  return prm.K <= 32 ? rk_by_score<T, 1>(stream, prm, form) : rk_by_score<T, 2>(stream, prm, form);
+}
+int rk_dispatch(void* stream, int dtype, const RkParams& prm, int mode) {
+  const unsigned form = rk_form(prm, mode, dtype);
+  if (dtype == MINER_DTYPE_BF16) return rk_by_k<__bf16>(stream, prm, form);
+  if (dtype == MINER_DTYPE_F16) return rk_by_k<_Float16>(stream, prm, form);
+  return rk_by_k<float>(stream, prm, form);
 }
 
-template <class T, int NKT, int S>
-int rk_launch(void* stream, const RkParams& prm) {
-  if (prm.clus != nullptr)
-    return prm.ids != nullptr ? rk_launch_cap<T, NKT, S, true>(stream, prm) : rk_launch_cap<T, NKT, S, false>(stream, prm);
-  const bool split = rk_split(prm);
-  // the cursor form: one instantiation per shape (table / subset, split or not), on the biased form
-  // with the prior tested at run time and either filter null or not
-  if (prm.aft_s != nullptr)
-    return prm.ids != nullptr ? rk_launch_geo<T, NKT, S, 0, true, true, true, true>(stream, prm, split)
-                              : rk_launch_geo<T, NKT, S, 0, true, false, true, true>(stream, prm, split);
-  const bool flt = prm.ok != nullptr || prm.E > 0;     // the filtered instantiation only when asked for
-  // the subset form: one instantiation per shape, the filtered one (either filter may be null),
-  // with the chunk count and K chosen as for the table forms
-  // the biased forms: filtered (as the subset form, either filter may be null), GEO 0
-  if (prm.bias != nullptr)
-    return prm.ids != nullptr ? rk_launch_geo<T, NKT, S, 0, true, true, true>(stream, prm, split)
-                              : rk_launch_geo<T, NKT, S, 0, true, false, true>(stream, prm, split);
-  if (prm.ids != nullptr) return rk_launch_geo<T, NKT, S, 0, true, true>(stream, prm, split);
-  // (GEO 1 — 64-byte rows through a 4-stage ring, three chunks in flight instead of one — measured
-  // slower: 95.9 vs 89.7 ms per config-5 step, twice the barriers for no gain in the gather rate;
-  // diagnostic builds with -DMINER_RK_GEO1 launch it)
-#ifdef MINER_RK_GEO1
-  constexpr int NR = S == MINER_SCORE_WEIGHTED ? 2 * NKT : NKT;
-  if constexpr (sizeof(T) == 2 && NR >= 2)
-    return flt ? rk_launch_geo<T, NKT, S, 1, true>(stream, prm, split) : rk_launch_geo<T, NKT, S, 1, false>(stream, prm, split);
-#endif
-  return flt ? rk_launch_geo<T, NKT, S, 0, true>(stream, prm, split) : rk_launch_geo<T, NKT, S, 0, false>(stream, prm, split);
+int check_dims(int dtype, int d, int Dc, int K) {
+  if (!dtype_ok(dtype) || d <= 0 || K <= 0 || Dc <= 0) return MINER_EINVAL;
+  if (K > kMaxK || Dc > 32 * kDcT || d > kMaxD) return MINER_ESHAPE;
+  if (d % (dtype == MINER_DTYPE_F32 ? 32 : 64)) return MINER_ESHAPE;
+  return MINER_OK;
 }
 
-// the counting and pair forms (MODE kCount / kPair): unsplit, GEO 0, the chunk count and K
-// compile-time by rk_launch_geo's rule (d = 768, and K = 64, in 16-bit) — a pair's score has the
-// bits of the ranking form that the same shape launches
-template <class T, int NKT, int S, int MODE, bool BIAS>
-int rk_launch_form(void* stream, const RkParams& prm) {
-  constexpr bool P = MODE == kPair;              // the pair form gathers: SUB (and so FLT)
-  void (*kern)(RkParams) = rk_fused<T, NKT, S, 0, 1, 0, 0, P, P, MODE, BIAS>;
-  if constexpr (sizeof(T) == 2) {
-    constexpr int kN768 = 768 * 2 / kRB<0>;
-    if (prm.d == 768) {
-      kern = rk_fused<T, NKT, S, kN768, 1, 0, 0, P, P, MODE, BIAS>;
-      if constexpr (NKT == 2)
-        if (prm.K == 64) kern = rk_fused<T, NKT, S, kN768, 1, 0, 64, P, P, MODE, BIAS>;
-    }
-  }
-  constexpr int NR = S == MINER_SCORE_WEIGHTED ? 2 * NKT : NKT;
-  const int lds = RkLds<NR, 0, P>::kTotal;
-  hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-  if (e != hipSuccess) return (int)e;
-  const int ntiles = P ? prm.U : (prm.U + kUT - 1) / kUT;
-  const int grid = num_cus() < ntiles ? num_cus() : ntiles;
-  hipLaunchKernelGGL(kern, dim3(grid), dim3(kThreads), lds, static_cast<hipStream_t>(stream), prm);
-  e = hipGetLastError();
-  return e == hipSuccess ? MINER_OK : (int)e;
-}
-
-template <class T, int MODE, bool BIAS>
-int rk_dispatch_form(void* stream, const RkParams& prm) {
-  const int st = prm.score_type;
-  if (prm.K <= 32) {
-    if (st == MINER_SCORE_WEIGHTED) return rk_launch_form<T, 1, MINER_SCORE_WEIGHTED, MODE, BIAS>(stream, prm);
-    if (st == MINER_SCORE_MAX) return rk_launch_form<T, 1, MINER_SCORE_MAX, MODE, BIAS>(stream, prm);
-    return rk_launch_form<T, 1, MINER_SCORE_MEAN, MODE, BIAS>(stream, prm);
-  }
-  if (st == MINER_SCORE_WEIGHTED) return rk_launch_form<T, 2, MINER_SCORE_WEIGHTED, MODE, BIAS>(stream, prm);
-  if (st == MINER_SCORE_MAX) return rk_launch_form<T, 2, MINER_SCORE_MAX, MODE, BIAS>(stream, prm);
-  return rk_launch_form<T, 2, MINER_SCORE_MEAN, MODE, BIAS>(stream, prm);
-}
-
-// (the biased instantiation only when a prior table was given: the unbiased calls launch what they did)
-template <int MODE, bool BIAS>
-int rk_run_form_b(void* stream, int dtype, const RkParams& prm) {
-  if (dtype == MINER_DTYPE_BF16) return rk_dispatch_form<__bf16, MODE, BIAS>(stream, prm);
-  if (dtype == MINER_DTYPE_F16) return rk_dispatch_form<_Float16, MODE, BIAS>(stream, prm);
-  return rk_dispatch_form<float, MODE, BIAS>(stream, prm);
-}
-template <int MODE>
-int rk_run_form(void* stream, int dtype, const RkParams& prm) {
-  return prm.bias != nullptr ? rk_run_form_b<MODE, true>(stream, dtype, prm) : rk_run_form_b<MODE, false>(stream, dtype, prm);
-}
-
-// the prior table's checks, shared by the three biased entry points (after each one's own)
-int bias_check(const float* news_bias, int G, const int32_t* user_group) {
-  if (news_bias != nullptr && G <= 0) return MINER_EINVAL;
-  if (news_bias == nullptr && user_group != nullptr) return MINER_EINVAL;
-  if (!aligned4(news_bias)) return MINER_EALIGN;
-  if (!aligned4(user_group)) return MINER_EALIGN;
+// the prior table's checks, shared by the three biased entry points (after each one's own); G and
+// the group ids are read only with a table
+int bias_check(RkParams& prm) {
+  if (prm.bias != nullptr && prm.G <= 0) return MINER_EINVAL;
+  if (prm.bias == nullptr && prm.grp != nullptr) return MINER_EINVAL;
+  if (!aligned4(prm.bias)) return MINER_EALIGN;
+  if (!aligned4(prm.grp)) return MINER_EALIGN;
+  if (prm.bias == nullptr) prm.G = 0;
   return MINER_OK;
 }
 
@@ -1666,98 +1653,63 @@ int cap_check(const int32_t* news_cluster, int cap) {
   return MINER_OK;
 }
 
-template <class T>
-int rk_dispatch(void* stream, const RkParams& prm) {
-  const int st = prm.score_type;
-  if (prm.K <= 32) {
-    if (st == MINER_SCORE_WEIGHTED) return rk_launch<T, 1, MINER_SCORE_WEIGHTED>(stream, prm);
-    if (st == MINER_SCORE_MAX) return rk_launch<T, 1, MINER_SCORE_MAX>(stream, prm);
-    return rk_launch<T, 1, MINER_SCORE_MEAN>(stream, prm);
-  }
-  if (st == MINER_SCORE_WEIGHTED) return rk_launch<T, 2, MINER_SCORE_WEIGHTED>(stream, prm);
-  if (st == MINER_SCORE_MAX) return rk_launch<T, 2, MINER_SCORE_MAX>(stream, prm);
-  return rk_launch<T, 2, MINER_SCORE_MEAN>(stream, prm);
-}
-
-int check_dims(int dtype, int d, int Dc, int K) {
-  if (!dtype_ok(dtype) || d <= 0 || K <= 0 || Dc <= 0) return MINER_EINVAL;
-  if (K > kMaxK || Dc > 32 * kDcT || d > kMaxD) return MINER_ESHAPE;
-  if (d % (dtype == MINER_DTYPE_F32 ? 32 : 64)) return MINER_ESHAPE;
+// the checks every entry point of the ranker starts with, on its arguments as prm holds them; the
+// list entries (rank) also answer for topk and the two list outputs, at their places in the order
+int rk_check_common(int dtype, const RkParams& prm, bool rank) {
+  const int ck = check_dims(dtype, prm.d, 1, prm.K);
+  if (ck != MINER_OK) return ck;
+  if (prm.score_type < MINER_SCORE_WEIGHTED || prm.score_type > MINER_SCORE_MEAN) return MINER_EINVAL;
+  if (prm.U < 0 || prm.N <= 0 || (rank && prm.topk <= 0)) return MINER_EINVAL;
+  if (rank && prm.topk > kMaxTopk) return MINER_ESHAPE;
+  if (!prm.mui || !prm.news || (rank && (!prm.top_s || !prm.top_i))) return MINER_EINVAL;
+  if (prm.score_type == MINER_SCORE_WEIGHTED && !prm.proj) return MINER_EINVAL;
+  if (!aligned16(prm.mui) || !aligned16(prm.proj) || !aligned16(prm.news)) return MINER_EALIGN;
   return MINER_OK;
 }
 
-// miner_rank_topk_filtered and miner_rank_topk_subset (subset: the id list's checks follow the
-// table forms' checks, which keep their order and codes)
-int rk_run(void* stream, int dtype, int score_type, const void* user_mui, const void* user_proj, const void* news, int U,
-           int N, int d, int K, int topk, const int32_t* exclude_ids, int E, const uint32_t* news_ok, bool subset,
-           const int32_t* news_ids, int M, float* top_scores, int32_t* top_ids, void* workspace, size_t workspace_bytes,
-           const float* news_bias = nullptr, int G = 0, const int32_t* user_group = nullptr,
-           const int32_t* news_cluster = nullptr, int cap = 0, const float* after_scores = nullptr,
-           const int32_t* after_ids = nullptr) {
-  const int ck = check_dims(dtype, d, 1, K);
+// every miner_rank_topk* entry point: prm holds the arguments as the caller gave them (the widest
+// entry's; the whole table is a NULL id list with M < 0); what a feature left NULL does not read is
+// cleared once the checks have passed. The id list's checks follow the table forms' checks, which
+// keep their order and codes.
+int rk_run(void* stream, int dtype, RkParams prm, void* workspace, size_t workspace_bytes) {
+  const int ck = rk_check_common(dtype, prm, true);
   if (ck != MINER_OK) return ck;
-  if (score_type < MINER_SCORE_WEIGHTED || score_type > MINER_SCORE_MEAN) return MINER_EINVAL;
-  if (U < 0 || N <= 0 || topk <= 0) return MINER_EINVAL;
-  if (topk > kMaxTopk) return MINER_ESHAPE;
-  if (!user_mui || !news || !top_scores || !top_ids) return MINER_EINVAL;
-  if (score_type == MINER_SCORE_WEIGHTED && !user_proj) return MINER_EINVAL;
-  if (!aligned16(user_mui) || !aligned16(user_proj) || !aligned16(news)) return MINER_EALIGN;
-  if (E < 0 || (E > 0 && !exclude_ids)) return MINER_EINVAL;
-  if (E > kMaxL) return MINER_ESHAPE;
-  if (!aligned4(exclude_ids) || !aligned4(news_ok)) return MINER_EALIGN;
+  if (prm.E < 0 || (prm.E > 0 && !prm.excl)) return MINER_EINVAL;
+  if (prm.E > kMaxL) return MINER_ESHAPE;
+  if (!aligned4(prm.excl) || !aligned4(prm.ok)) return MINER_EALIGN;
+  const bool subset = prm.ids != nullptr || prm.M >= 0;
   if (subset) {
-    if (M < 0 || (M > 0 && !news_ids)) return MINER_EINVAL;
-    if (!aligned4(news_ids)) return MINER_EALIGN;
+    if (prm.M < 0 || (prm.M > 0 && !prm.ids)) return MINER_EINVAL;
+    if (!aligned4(prm.ids)) return MINER_EALIGN;
   }
-  const int bk = bias_check(news_bias, G, user_group);
+  const int bk = bias_check(prm);
   if (bk != MINER_OK) return bk;
-  const int cc = cap_check(news_cluster, cap);
+  const int cc = cap_check(prm.clus, prm.cap);
   if (cc != MINER_OK) return cc;
-  if (!aligned4(news_cluster)) return MINER_EALIGN;
+  if (!aligned4(prm.clus)) return MINER_EALIGN;
   // the cursor: both words or neither, never with caps (a capped walk also needs the earlier pages'
   // per-cluster counts, which a (score, id) pair does not carry)
-  if ((after_scores == nullptr) != (after_ids == nullptr)) return MINER_EINVAL;
-  if (after_scores != nullptr && news_cluster != nullptr) return MINER_EINVAL;
-  if (!aligned4(after_scores) || !aligned4(after_ids)) return MINER_EALIGN;
-  if (U == 0) return MINER_OK;
-  RkParams prm{};
+  if ((prm.aft_s == nullptr) != (prm.aft_i == nullptr)) return MINER_EINVAL;
+  if (prm.aft_s != nullptr && prm.clus != nullptr) return MINER_EINVAL;
+  if (!aligned4(prm.aft_s) || !aligned4(prm.aft_i)) return MINER_EALIGN;
+  if (prm.U == 0) return MINER_OK;
   if (!aligned16(workspace)) return MINER_EALIGN;
-  if (subset && M == 0) {                  // nothing to rank: every list empty, no ranker launch
-    const size_t n = (size_t)U * topk;
+  if (subset && prm.M == 0) {              // nothing to rank: every list empty, no ranker launch
+    const size_t n = (size_t)prm.U * prm.topk;
     hipLaunchKernelGGL(rk_fill_empty, dim3((unsigned)((n + 255) / 256 < 1024 ? (n + 255) / 256 : 1024)), dim3(256), 0,
-                       static_cast<hipStream_t>(stream), top_scores, top_ids, n);
+                       static_cast<hipStream_t>(stream), prm.top_s, prm.top_i, n);
     const hipError_t e = hipGetLastError();
     return e == hipSuccess ? MINER_OK : (int)e;
   }
-  prm.mui = user_mui; prm.proj = user_proj; prm.news = news; prm.top_s = top_scores; prm.top_i = top_ids;
   if (workspace) {
     prm.ws_bytes = workspace_bytes;
     prm.ws_s = static_cast<float*>(workspace);
-    prm.ws_i = reinterpret_cast<int32_t*>(static_cast<char*>(workspace) + (size_t)U * kSplit * topk * 4);
+    prm.ws_i = reinterpret_cast<int32_t*>(static_cast<char*>(workspace) + (size_t)prm.U * kSplit * prm.topk * 4);
   }
-  prm.U = U; prm.N = N; prm.d = d; prm.K = K; prm.topk = topk; prm.score_type = score_type;
-  prm.excl = E > 0 ? exclude_ids : nullptr; prm.E = E; prm.ok = news_ok;
-  prm.ids = subset ? news_ids : nullptr; prm.M = subset ? M : 0;
-  prm.bias = news_bias; prm.grp = news_bias ? user_group : nullptr; prm.G = news_bias ? G : 0;
-  prm.clus = news_cluster; prm.cap = news_cluster ? cap : 0;
-  prm.aft_s = after_scores; prm.aft_i = after_ids;
-  if (dtype == MINER_DTYPE_BF16) return rk_dispatch<__bf16>(stream, prm);
-  if (dtype == MINER_DTYPE_F16) return rk_dispatch<_Float16>(stream, prm);
-  return rk_dispatch<float>(stream, prm);
-}
-
-// the checks that miner_score_pairs and miner_rank_count share with rk_run, in its order and with
-// its codes (what they have no argument for — topk, the lists — left out)
-int rk_check_common(int dtype, int score_type, const void* user_mui, const void* user_proj, const void* news, int U, int N,
-                    int d, int K) {
-  const int ck = check_dims(dtype, d, 1, K);
-  if (ck != MINER_OK) return ck;
-  if (score_type < MINER_SCORE_WEIGHTED || score_type > MINER_SCORE_MEAN) return MINER_EINVAL;
-  if (U < 0 || N <= 0) return MINER_EINVAL;
-  if (!user_mui || !news) return MINER_EINVAL;
-  if (score_type == MINER_SCORE_WEIGHTED && !user_proj) return MINER_EINVAL;
-  if (!aligned16(user_mui) || !aligned16(user_proj) || !aligned16(news)) return MINER_EALIGN;
-  return MINER_OK;
+  if (prm.E == 0) prm.excl = nullptr;
+  if (!subset) { prm.ids = nullptr; prm.M = 0; }
+  if (prm.clus == nullptr) prm.cap = 0;
+  return rk_dispatch(stream, dtype, prm, kRank);
 }
 
 }  // namespace
@@ -1773,19 +1725,19 @@ int miner_score_pairs(void* stream, int dtype, int score_type, const void* user_
 int miner_score_pairs_biased(void* stream, int dtype, int score_type, const void* user_mui, const void* user_proj,
                              const void* news, int U, int N, int d, int K, const int32_t* cand_ids, int C, float* scores,
                              const float* news_bias, int G, const int32_t* user_group) {
-  const int ck = rk_check_common(dtype, score_type, user_mui, user_proj, news, U, N, d, K);
-  if (ck != MINER_OK) return ck;
-  if (C < 0 || (C > 0 && (!cand_ids || !scores))) return MINER_EINVAL;
-  if (!aligned4(cand_ids) || !aligned4(scores)) return MINER_EALIGN;
-  const int bk = bias_check(news_bias, G, user_group);
-  if (bk != MINER_OK) return bk;
-  if (U == 0 || C == 0) return MINER_OK;
   RkParams prm{};
   prm.mui = user_mui; prm.proj = user_proj; prm.news = news; prm.top_s = scores;
   prm.U = U; prm.N = N; prm.d = d; prm.K = K; prm.score_type = score_type;
   prm.ids = cand_ids; prm.M = C;
-  prm.bias = news_bias; prm.grp = news_bias ? user_group : nullptr; prm.G = news_bias ? G : 0;
-  return rk_run_form<kPair>(stream, dtype, prm);
+  prm.bias = news_bias; prm.grp = user_group; prm.G = G;
+  const int ck = rk_check_common(dtype, prm, false);
+  if (ck != MINER_OK) return ck;
+  if (C < 0 || (C > 0 && (!cand_ids || !scores))) return MINER_EINVAL;
+  if (!aligned4(cand_ids) || !aligned4(scores)) return MINER_EALIGN;
+  const int bk = bias_check(prm);
+  if (bk != MINER_OK) return bk;
+  if (U == 0 || C == 0) return MINER_OK;
+  return rk_dispatch(stream, dtype, prm, kPair);
 }
 
 int miner_rank_count(void* stream, int dtype, int score_type, const void* user_mui, const void* user_proj,
@@ -1799,20 +1751,20 @@ int miner_rank_count_biased(void* stream, int dtype, int score_type, const void*
                             const void* news, int U, int N, int d, int K, const float* target_scores,
                             const int32_t* target_ids, int T, const uint32_t* news_ok, int32_t* counts,
                             const float* news_bias, int G, const int32_t* user_group) {
-  const int ck = rk_check_common(dtype, score_type, user_mui, user_proj, news, U, N, d, K);
-  if (ck != MINER_OK) return ck;
-  if (T <= 0 || !target_scores || !target_ids || !counts) return MINER_EINVAL;
-  if (T > kMaxT) return MINER_ESHAPE;
-  if (!aligned4(target_scores) || !aligned4(target_ids) || !aligned4(news_ok) || !aligned4(counts)) return MINER_EALIGN;
-  const int bk = bias_check(news_bias, G, user_group);
-  if (bk != MINER_OK) return bk;
-  if (U == 0) return MINER_OK;
   RkParams prm{};
   prm.mui = user_mui; prm.proj = user_proj; prm.news = news; prm.top_i = counts;
   prm.U = U; prm.N = N; prm.d = d; prm.K = K; prm.score_type = score_type;
   prm.ok = news_ok; prm.tgt_s = target_scores; prm.tgt_i = target_ids; prm.T = T;
-  prm.bias = news_bias; prm.grp = news_bias ? user_group : nullptr; prm.G = news_bias ? G : 0;
-  return rk_run_form<kCount>(stream, dtype, prm);
+  prm.bias = news_bias; prm.grp = user_group; prm.G = G;
+  const int ck = rk_check_common(dtype, prm, false);
+  if (ck != MINER_OK) return ck;
+  if (T <= 0 || !target_scores || !target_ids || !counts) return MINER_EINVAL;
+  if (T > kMaxT) return MINER_ESHAPE;
+  if (!aligned4(target_scores) || !aligned4(target_ids) || !aligned4(news_ok) || !aligned4(counts)) return MINER_EALIGN;
+  const int bk = bias_check(prm);
+  if (bk != MINER_OK) return bk;
+  if (U == 0) return MINER_OK;
+  return rk_dispatch(stream, dtype, prm, kCount);
 }
 
 size_t miner_encoder_packed_bytes(int dtype, int d, int Dc, int K) {
@@ -1890,16 +1842,21 @@ int miner_rank_topk_filtered(void* stream, int dtype, int score_type, const void
                              const void* news, int U, int N, int d, int K, int topk, const int32_t* exclude_ids, int E,
                              const uint32_t* news_ok, float* top_scores, int32_t* top_ids, void* workspace,
                              size_t workspace_bytes) {
-  return rk_run(stream, dtype, score_type, user_mui, user_proj, news, U, N, d, K, topk, exclude_ids, E, news_ok, false,
-                nullptr, 0, top_scores, top_ids, workspace, workspace_bytes);
+  return miner_rank_topk_after(stream, dtype, score_type, user_mui, user_proj, news, U, N, d, K, topk, exclude_ids, E, news_ok,
+                               nullptr, -1, top_scores, top_ids, workspace, workspace_bytes, nullptr, 0, nullptr, nullptr, 0,
+                               nullptr, nullptr);
 }
 
 int miner_rank_topk_subset(void* stream, int dtype, int score_type, const void* user_mui, const void* user_proj,
                            const void* news, int U, int N, int d, int K, int topk, const int32_t* exclude_ids, int E,
                            const uint32_t* news_ok, const int32_t* news_ids, int M, float* top_scores, int32_t* top_ids,
                            void* workspace, size_t workspace_bytes) {
-  return rk_run(stream, dtype, score_type, user_mui, user_proj, news, U, N, d, K, topk, exclude_ids, E, news_ok, true,
-                news_ids, M, top_scores, top_ids, workspace, workspace_bytes);
+  // Here a NULL list with M < 0 is an error, for the wider entries it is the whole table: that pair
+  // goes on with a list pointer that is never read, so that M < 0 answers at the list's check.
+  static const int32_t no_list = 0;
+  return miner_rank_topk_after(stream, dtype, score_type, user_mui, user_proj, news, U, N, d, K, topk, exclude_ids, E, news_ok,
+                               news_ids == nullptr && M < 0 ? &no_list : news_ids, M, top_scores, top_ids, workspace,
+                               workspace_bytes, nullptr, 0, nullptr, nullptr, 0, nullptr, nullptr);
 }
 
 int miner_rank_topk_biased(void* stream, int dtype, int score_type, const void* user_mui, const void* user_proj,
@@ -1907,10 +1864,9 @@ int miner_rank_topk_biased(void* stream, int dtype, int score_type, const void* 
                            const uint32_t* news_ok, const int32_t* news_ids, int M, float* top_scores, int32_t* top_ids,
                            void* workspace, size_t workspace_bytes, const float* news_bias, int G,
                            const int32_t* user_group) {
-  const bool table = news_ids == nullptr && M < 0;     // the whole table: the filtered form
-  return rk_run(stream, dtype, score_type, user_mui, user_proj, news, U, N, d, K, topk, exclude_ids, E, news_ok, !table,
-                table ? nullptr : news_ids, table ? 0 : M, top_scores, top_ids, workspace, workspace_bytes, news_bias, G,
-                user_group);
+  return miner_rank_topk_after(stream, dtype, score_type, user_mui, user_proj, news, U, N, d, K, topk, exclude_ids, E, news_ok,
+                               news_ids, M, top_scores, top_ids, workspace, workspace_bytes, news_bias, G, user_group, nullptr,
+                               0, nullptr, nullptr);
 }
 
 int miner_rank_topk_capped(void* stream, int dtype, int score_type, const void* user_mui, const void* user_proj,
@@ -1918,10 +1874,9 @@ int miner_rank_topk_capped(void* stream, int dtype, int score_type, const void* 
                            const uint32_t* news_ok, const int32_t* news_ids, int M, float* top_scores, int32_t* top_ids,
                            void* workspace, size_t workspace_bytes, const float* news_bias, int G,
                            const int32_t* user_group, const int32_t* news_cluster, int cap) {
-  const bool table = news_ids == nullptr && M < 0;     // the whole table: the filtered form
-  return rk_run(stream, dtype, score_type, user_mui, user_proj, news, U, N, d, K, topk, exclude_ids, E, news_ok, !table,
-                table ? nullptr : news_ids, table ? 0 : M, top_scores, top_ids, workspace, workspace_bytes, news_bias, G,
-                user_group, news_cluster, cap);
+  return miner_rank_topk_after(stream, dtype, score_type, user_mui, user_proj, news, U, N, d, K, topk, exclude_ids, E, news_ok,
+                               news_ids, M, top_scores, top_ids, workspace, workspace_bytes, news_bias, G, user_group,
+                               news_cluster, cap, nullptr, nullptr);
 }
 
 int miner_rank_topk_after(void* stream, int dtype, int score_type, const void* user_mui, const void* user_proj,
@@ -1930,10 +1885,15 @@ int miner_rank_topk_after(void* stream, int dtype, int score_type, const void* u
                           void* workspace, size_t workspace_bytes, const float* news_bias, int G,
                           const int32_t* user_group, const int32_t* news_cluster, int cap, const float* after_scores,
                           const int32_t* after_ids) {
-  const bool table = news_ids == nullptr && M < 0;     // the whole table: the filtered form
-  return rk_run(stream, dtype, score_type, user_mui, user_proj, news, U, N, d, K, topk, exclude_ids, E, news_ok, !table,
-                table ? nullptr : news_ids, table ? 0 : M, top_scores, top_ids, workspace, workspace_bytes, news_bias, G,
-                user_group, news_cluster, cap, after_scores, after_ids);
+  RkParams prm{};
+  prm.mui = user_mui; prm.proj = user_proj; prm.news = news; prm.top_s = top_scores; prm.top_i = top_ids;
+  prm.U = U; prm.N = N; prm.d = d; prm.K = K; prm.topk = topk; prm.score_type = score_type;
+  prm.excl = exclude_ids; prm.E = E; prm.ok = news_ok;
+  prm.ids = news_ids; prm.M = M;           // the whole table: a NULL list with M < 0
+  prm.bias = news_bias; prm.grp = user_group; prm.G = G;
+  prm.clus = news_cluster; prm.cap = cap;
+  prm.aft_s = after_scores; prm.aft_i = after_ids;
+  return rk_run(stream, dtype, prm, workspace, workspace_bytes);
 }
 
 int miner_topk_merge(void* stream, const float* a_scores, const int32_t* a_ids, int ka, const float* b_scores,
