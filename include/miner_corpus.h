@@ -28,6 +28,11 @@
  *   miner_rank_topk_capped(...), miner_topk_merge_capped(...)
  *                             the ranking and list-merge forms with at most `cap` news of one
  *                             cluster (story, publisher) per list.
+ *   miner_rank_topk_after(...)     the ranking continued strictly after a (score, id) cursor per user.
+ *   miner_score_pairs_interest(...), miner_rank_topk_interest(...), miner_topk_merge_grouped(...)
+ *                             which of the user's K interests a news matched (the arg-max of the
+ *                             score's own reduction over K), and lists with at most `interest_cap`
+ *                             news of one dominant interest.
  *
  * Conventions are those of miner_score.h. dtype: MINER_DTYPE_F32 (exact fp32, parity mode),
  * MINER_DTYPE_BF16 or MINER_DTYPE_F16 (16-bit operands, fp32 accumulation and softmax).
@@ -328,6 +333,78 @@ int miner_rank_topk_after(void* stream, int dtype, int score_type, const void* u
                           void* workspace, size_t workspace_bytes, const float* news_bias, int G,
                           const int32_t* user_group, const int32_t* news_cluster, int cap,
                           const float* after_scores, const int32_t* after_ids);
+
+/*
+ * The dominant interest of a pair, and per-interest caps: what MINER's K interest vectors add to a
+ * served list — which of the user's interests a news matched, and lists that cover several of them.
+ *   interest(u, n) = the lowest k in [0, K) whose value equals the maximum the score's own reduction
+ *   over K found: for MINER_SCORE_WEIGHTED over the logits proj_k · e_n (the largest target-aware
+ *   softmax weight, model.py:213), for MINER_SCORE_MAX over M_k = mui_k · e_n (model.py:129). It is
+ *   read off the very accumulators the score is made from, after the contraction, so no score bit
+ *   changes; ties go to the lowest k; if no k compares equal (every value NaN) it is -1, "in no
+ *   group". A prior (news_bias) does not enter it. MINER_SCORE_MEAN has no dominant interest: asking
+ *   for one is MINER_EINVAL.
+ *
+ * miner_score_pairs_interest: miner_score_pairs_biased's arguments, then
+ *   interests   [U, C] int32 out, device pointer, 4-byte aligned: interest(u, cand_ids[u, c]) next to
+ *               scores[u, c]; -1 for an id outside [0, N).
+ * scores are, bit for bit, miner_score_pairs_biased's. With interests NULL it returns exactly what
+ * miner_score_pairs_biased returns: it launches the same kernel. After that call's own checks, in
+ * their order and with their codes: interests with MINER_SCORE_MEAN: MINER_EINVAL; a misaligned
+ * interests: MINER_EALIGN (all before any launch, and before the U == 0 / C == 0 returns).
+ *
+ * miner_rank_topk_interest: miner_rank_topk_after's arguments, then
+ *   interest_cap  0: none — with top_interest NULL the call returns exactly what
+ *               miner_rank_topk_after returns on the other arguments (it launches the same kernel);
+ *               1 <= interest_cap <= MINER_CORPUS_MAX_TOPK: at most interest_cap news of one
+ *               dominant interest in a user's list.
+ *   top_interest  [U, topk] int32 out or NULL (only under a cap), 4-byte aligned: interest(u, .) of
+ *               the listed entries, -1 in the (-inf, -1) tail.
+ * User u's list is the walk of its complete ranking — under exclude_ids, news_ok, news_ids and
+ * news_bias, as the uncapped call gives it with topk = N — that keeps an entry iff fewer than
+ * interest_cap kept entries before it have the same interest(u, .); an entry with interest -1 is
+ * always kept; the walk stops after topk kept entries, then (-inf, -1). A listed score is the uncapped
+ * call's, bit for bit. This is exactly miner_rank_topk_capped for that one user with the cluster
+ * table g_u[n] = interest(u, n) (news_cluster cannot express it for more than one user: its cluster
+ * belongs to the news, the dominant interest to the pair). As the capped form: the UNSPLIT kernel
+ * whatever the workspace (accepted, never written), over the table or the id list, with or without
+ * a prior; no cursor, and never together with news_cluster. After miner_rank_topk_after's own
+ * checks, in their order and with their codes: interest_cap < 0: MINER_EINVAL;
+ * interest_cap > MINER_CORPUS_MAX_TOPK: MINER_ESHAPE; a cap with a non-NULL news_cluster or with a
+ * cursor: MINER_EINVAL; a cap with MINER_SCORE_MEAN: MINER_EINVAL; top_interest without a cap:
+ * MINER_EINVAL; a misaligned top_interest: MINER_EALIGN (all before any launch, and before the
+ * U == 0 return).
+ *
+ * miner_topk_merge_grouped: miner_topk_merge's arguments, then per-entry groups and a cap —
+ *   a_groups [U, ka], b_groups [U, kb] int32: the group of each entry (its interest; < 0: none),
+ *   out_groups [U, topk] int32 out: the groups of the merged entries, -1 in the tail,
+ *   cap         0: the groups are only carried; 1 <= cap <= MINER_CORPUS_MAX_TOPK: after the
+ *               replacement and the pruning, the capped walk of miner_topk_merge_capped over what is
+ *               left, with an entry's own group in place of news_cluster[id].
+ * An id in both rows keeps b's entry and b's group. With cap == 0 out_scores / out_ids are
+ * miner_topk_merge's, bit for bit. Interest-capped lists of one user merge as capped lists do:
+ * for disjoint id sets the result is the interest-capped ranking of their union, bit for bit. After
+ * miner_topk_merge's own checks, in their order and with their codes: cap < 0: MINER_EINVAL;
+ * cap > MINER_CORPUS_MAX_TOPK: MINER_ESHAPE; a NULL a_groups with ka > 0, b_groups with kb > 0, or
+ * out_groups: MINER_EINVAL; a misaligned group pointer: MINER_EALIGN (all before any launch, and
+ * before the U == 0 return).
+ */
+int miner_score_pairs_interest(void* stream, int dtype, int score_type, const void* user_mui,
+                               const void* user_proj, const void* news, int U, int N, int d, int K,
+                               const int32_t* cand_ids, int C, float* scores, const float* news_bias, int G,
+                               const int32_t* user_group, int32_t* interests);
+int miner_rank_topk_interest(void* stream, int dtype, int score_type, const void* user_mui,
+                             const void* user_proj, const void* news, int U, int N, int d, int K, int topk,
+                             const int32_t* exclude_ids, int E, const uint32_t* news_ok,
+                             const int32_t* news_ids, int M, float* top_scores, int32_t* top_ids,
+                             void* workspace, size_t workspace_bytes, const float* news_bias, int G,
+                             const int32_t* user_group, const int32_t* news_cluster, int cap,
+                             const float* after_scores, const int32_t* after_ids, int interest_cap,
+                             int32_t* top_interest);
+int miner_topk_merge_grouped(void* stream, const float* a_scores, const int32_t* a_ids, int ka,
+                             const float* b_scores, const int32_t* b_ids, int kb, int U, int topk,
+                             const uint32_t* news_ok, int N, float* out_scores, int32_t* out_ids,
+                             const int32_t* a_groups, const int32_t* b_groups, int32_t* out_groups, int cap);
 
 #ifdef __cplusplus
 }

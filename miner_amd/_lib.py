@@ -63,6 +63,10 @@ SIGNATURES = {
     "miner_topk_merge_capped": (_I, [_P, _P, _P, _I, _P, _P, _I, _I, _I, _P, _I, _P, _P, _P, _I, _I]),
     "miner_rank_topk_after": (_I, [_P, _I, _I, _P, _P, _P, _I, _I, _I, _I, _I, _P, _I, _P, _P, _I, _P, _P, _P,
                                    ctypes.c_size_t, _P, _I, _P, _P, _I, _P, _P]),
+    "miner_score_pairs_interest": (_I, [_P, _I, _I, _P, _P, _P, _I, _I, _I, _I, _P, _I, _P, _P, _I, _P, _P]),
+    "miner_rank_topk_interest": (_I, [_P, _I, _I, _P, _P, _P, _I, _I, _I, _I, _I, _P, _I, _P, _P, _I, _P, _P, _P,
+                                      ctypes.c_size_t, _P, _I, _P, _P, _I, _P, _P, _I, _P]),
+    "miner_topk_merge_grouped": (_I, [_P, _P, _P, _I, _P, _P, _I, _I, _I, _P, _I, _P, _P, _P, _P, _P, _I]),
     # include/miner_news.h
     "miner_news_precompute": (_I, [_P, _I, _P, _I, _P, _I, _I, _I, _P, _P]),
     "miner_score_news": (_I, [_P, _I, _I, _P, _P, _P, _I, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P]),

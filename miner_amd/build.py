@@ -123,6 +123,7 @@ ASAN_DRIVER_RANK = os.path.join(ROOT, "tests", "native", "abi_errors_rank.cpp")
 ASAN_DRIVER_BIAS = os.path.join(ROOT, "tests", "native", "abi_errors_bias.cpp")
 ASAN_DRIVER_CAP = os.path.join(ROOT, "tests", "native", "abi_errors_cap.cpp")
 ASAN_DRIVER_AFTER = os.path.join(ROOT, "tests", "native", "abi_errors_after.cpp")
+ASAN_DRIVER_INTEREST = os.path.join(ROOT, "tests", "native", "abi_errors_interest.cpp")
 
 
 def build_asan_driver(force: bool = False, verbose: bool = False, driver: str = ASAN_DRIVER) -> str:
@@ -199,6 +200,13 @@ def build_asan_driver_after(force: bool = False, verbose: bool = False) -> str:
     return build_asan_driver(force=force, verbose=verbose, driver=ASAN_DRIVER_AFTER)
 
 
+def build_asan_driver_interest(force: bool = False, verbose: bool = False) -> str:
+    """build/asan/abi_errors_interest: the error paths of miner_score_pairs_interest,
+    miner_rank_topk_interest and miner_topk_merge_grouped (tests/native/abi_errors_interest.cpp; run
+    by tests/test_corpus_interest_host.py)."""
+    return build_asan_driver(force=force, verbose=verbose, driver=ASAN_DRIVER_INTEREST)
+
+
 if __name__ == "__main__":
     if "--asan" in sys.argv:
         print(build_asan_driver(force="--force" in sys.argv, verbose=True))
@@ -207,5 +215,6 @@ if __name__ == "__main__":
         print(build_asan_driver_bias(verbose=True))
         print(build_asan_driver_cap(verbose=True))
         print(build_asan_driver_after(verbose=True))
+        print(build_asan_driver_interest(verbose=True))
     else:
         print(build_library(force="--force" in sys.argv, verbose=True, debug="--debug" in sys.argv))

@@ -22,6 +22,13 @@ d=768, fp16), backed by libminer_hip.so (include/miner_corpus.h).
                                                            # none) per list, inside the ranker's merge; also merge_topk,
                                                            # update_topk, rank_corpus; cap_topk(lists, story, 1) caps a
                                                            # served list (unsplit kernel only; not rank_of / score_pairs)
+    s, i, g = rank_topk(..., return_interest=True)         # g int32 [U,topk]: which of the user's K interests each
+                                                           # listed news matched (the arg-max of the score's own
+                                                           # reduction over K; 'weighted' / 'max'); also score_pairs,
+    rank_topk(..., interest_cap=3, return_interest=True)   # rank_topk_deep, rank_corpus. At most interest_cap news of one
+                                                           # dominant interest per list; triples through merge_topk /
+                                                           # update_topk(interest_cap=) (unsplit kernel only, no cursor;
+                                                           # not rank_of / evaluate_corpus / rescore_topk)
 
 The click score of (user, news) is the reference's (src/model/model.py:127-134, 213-214) with the
 impression's candidate set replaced by the whole news table; ties rank the lower news id first.
@@ -31,6 +38,7 @@ from __future__ import annotations
 
 import dataclasses
 import os
+import warnings
 from typing import Optional
 
 import torch
@@ -307,6 +315,26 @@ def _no_cursor_under_caps(after, news_cluster, cluster_cap) -> None:
         raise ValueError("after= cannot be combined with news_cluster / cluster_cap")
 
 
+def _interest_args(interest_cap, return_interest, score_type, news_cluster=None, cluster_cap=None, after=None) -> int:
+    """interest_cap= / return_interest= of the ranking entries -> the C entries' interest_cap (0: none).
+    Everything is checked before anything touches the device: the mean score has no dominant
+    interest; a per-interest cap is an int in [1, MAX_TOPK] and, as the per-cluster caps, has no
+    cursor — and the two kinds of caps do not combine (one group per entry in the ranker's merge)."""
+    if interest_cap is None and not return_interest:
+        return 0
+    if score_type == "mean":
+        raise ValueError("score_type 'mean' has no dominant interest: interest_cap / return_interest need 'weighted' or 'max'")
+    if interest_cap is None:
+        return 0
+    if isinstance(interest_cap, bool) or not isinstance(interest_cap, int) or not 1 <= interest_cap <= MAX_TOPK:
+        raise ValueError(f"interest_cap must be an int in [1, {MAX_TOPK}]")
+    if news_cluster is not None or cluster_cap is not None:
+        raise ValueError("interest_cap cannot be combined with news_cluster / cluster_cap")
+    if after is not None:
+        raise ValueError("interest_cap cannot be combined with after= (there is no cursor under caps)")
+    return interest_cap
+
+
 def start_cursor(U: int, device):
     """The cursor before everything, (+inf, -1) for each of U users: rank_topk(after=start_cursor(...))
     is the first page — the list of the call without a cursor."""
@@ -336,7 +364,7 @@ def rank_topk(user_mui: Tensor, user_proj: Optional[Tensor], news: Tensor, topk:
               score_type: str = "weighted", exclude_ids: Optional[Tensor] = None,
               eligible: Optional[Tensor] = None, news_ids=None, news_bias=None,
               user_group: Optional[Tensor] = None, news_cluster=None, cluster_cap: Optional[int] = None,
-              after=None):
+              after=None, interest_cap: Optional[int] = None, return_interest: bool = False):
     """Top-k news per user by the click score, best first: (scores [U,topk] fp32, ids [U,topk]
     int32); entries past the table size are (-inf, -1).
 
@@ -383,7 +411,28 @@ def rank_topk(user_mui: Tensor, user_proj: Optional[Tensor], news: Tensor, topk:
     be a listed, eligible or existing news: it is a position in the order. Each page streams the
     table once (the price: profiles/rk_after_ab.txt). There is no cursor under caps (a capped walk
     also needs the earlier pages' per-cluster counts): ``after`` with news_cluster / cluster_cap
-    raises ValueError. Without ``after`` the call is today's."""
+    raises ValueError. Without ``after`` the call is today's.
+
+    return_interest: the call returns (scores, ids, interests): interests int32 [U,topk], the
+    dominant interest of each listed pair — the lowest k in [0, K) whose value equals the maximum
+    the score's own reduction over K found ('weighted': the largest target-aware softmax weight,
+    model.py:213; 'max': the arg-max of M_k, model.py:129), -1 in the tail. Without interest_cap it is
+    the call without it followed by score_pairs(return_interest=True) on the returned ids: the list
+    is bit for bit the plain call's and no other ranking kernel runs.
+
+    interest_cap: an int in [1, 256]: at most interest_cap news of one dominant interest in a user's
+    list — the capped walk above with the pair's interest in place of the news's cluster (for one
+    user: news_cluster = that user's interests, which no table can say for several). Scores are the
+    uncapped call's, bit for bit. As the per-cluster caps: the unsplit kernel, no ``after``, and not
+    together with news_cluster / cluster_cap (ValueError). 'mean' has no dominant interest: either
+    argument with it raises ValueError. A list holds at most interest_cap · K entries: a larger topk
+    never fills, and a list that never fills merges every news of every step (5.15x the step at
+    cap 1, K = 64, topk = 100) — keep topk <= interest_cap · K; a call that does not gets a
+    RuntimeWarning (the list is still exact: the kernel does not clamp topk, because an entry in no
+    group — 'max' over a row whose M_k are all NaN scores -inf with interest -1 — is always kept, so
+    a list can hold more than interest_cap · K entries). The price otherwise, 1.01 - 1.03x the
+    capped step: profiles/rk_interest_ab.txt. With neither the call is today's."""
+    icap = _interest_args(interest_cap, return_interest, score_type, news_cluster, cluster_cap, after)
     _no_cursor_under_caps(after, news_cluster, cluster_cap)
     pri = _prior(news_bias, user_group, user_mui.shape[0], news.shape[0])
     caps = _caps(news_cluster, cluster_cap, news.shape[0])
@@ -393,6 +442,11 @@ def rank_topk(user_mui: Tensor, user_proj: Optional[Tensor], news: Tensor, topk:
     N = tab.shape[0]
     if not 1 <= topk <= MAX_TOPK:
         raise ValueError(f"topk must be in [1, {MAX_TOPK}]")
+    if icap and topk > icap * K:
+        # the result is right, the step is slow (see the docstring): say so once per call site
+        warnings.warn(f"rank_topk: topk={topk} exceeds interest_cap * K = {icap * K}: the list can never fill, so every "
+                      f"step merges all its news (several times the capped step); ask for topk <= {icap * K}",
+                      RuntimeWarning, stacklevel=2)
     _require_device(exclude_ids, eligible)
     excl, E = None, 0
     if exclude_ids is not None:
@@ -413,25 +467,32 @@ def rank_topk(user_mui: Tensor, user_proj: Optional[Tensor], news: Tensor, topk:
     lib = _lib.lib()
     force = os.environ.get("MINER_RK_SPLIT", "")
     split = force == "1" if force in ("0", "1") else bool(lib.miner_rank_topk_split_recommended(U))
-    split = split and caps is None
+    split = split and caps is None and icap == 0
     nws = int(lib.miner_rank_topk_workspace_bytes(U, topk)) if split else 0
     ws = torch.empty(nws, dtype=torch.uint8, device=dev) if nws else None
     M = -1 if sub is None else sub.ids.numel()               # -1 with no list: the whole table
+    top_g = torch.empty(U, topk, dtype=torch.int32, device=dev) if icap and return_interest else None
     with torch.cuda.device(dev):
         # the widest entry; what the call does not use is NULL and launches the narrower entry's kernel
-        rc = lib.miner_rank_topk_after(_stream(dev), dt, st, _ptr(mui), _ptr(proj), _ptr(tab), U, N, d, K, topk,
-                                       _ptr(excl), E, _ptr(ok), _ptr(sub.ids) if M > 0 else None, M, _ptr(top_s),
-                                       _ptr(top_i), _ptr(ws), nws, *_prior_args(pri),
-                                       None if caps is None else _ptr(caps.cluster), 0 if caps is None else caps.cap,
-                                       None if cur is None else _ptr(cur.scores), None if cur is None else _ptr(cur.ids))
+        rc = lib.miner_rank_topk_interest(_stream(dev), dt, st, _ptr(mui), _ptr(proj), _ptr(tab), U, N, d, K, topk,
+                                          _ptr(excl), E, _ptr(ok), _ptr(sub.ids) if M > 0 else None, M, _ptr(top_s),
+                                          _ptr(top_i), _ptr(ws), nws, *_prior_args(pri),
+                                          None if caps is None else _ptr(caps.cluster), 0 if caps is None else caps.cap,
+                                          None if cur is None else _ptr(cur.scores), None if cur is None else _ptr(cur.ids),
+                                          icap, _ptr(top_g))
     _lib.check(rc, "miner_rank_topk")
-    return top_s, top_i
+    if not return_interest:
+        return top_s, top_i
+    if top_g is None:        # no cap: the pair form on the listed ids (a tail id of -1 gives -1)
+        top_g = _score_pairs(st, dt, mui, proj, tab, top_i.to(torch.int64), None, True)[1]
+    return top_s, top_i, top_g
 
 
 def rank_topk_deep(user_mui: Tensor, user_proj: Optional[Tensor], news: Tensor, topk: int, *, after=None,
                    score_type: str = "weighted", exclude_ids: Optional[Tensor] = None,
                    eligible: Optional[Tensor] = None, news_ids=None, news_bias=None,
-                   user_group: Optional[Tensor] = None, news_cluster=None, cluster_cap=None):
+                   user_group: Optional[Tensor] = None, news_cluster=None, cluster_cap=None, interest_cap=None,
+                   return_interest: bool = False):
     """rank_topk for any topk >= 1: (scores [U,topk] fp32, ids [U,topk] int32), best first, with the
     (-inf, -1) tail — ceil(topk / 256) pages of rank_topk chained with page_cursor (the first from
     ``after``, or from the top without it) and written side by side. Every page streams the table
@@ -439,9 +500,14 @@ def rank_topk_deep(user_mui: Tensor, user_proj: Optional[Tensor], news: Tensor, 
     list is paid for by its depth. The other arguments are rank_topk's; ``news_ids`` is canonicalised
     once, the bitmap packed once and the prior checked once. No host synchronisation beyond
     rank_topk's own argument checks. Per-cluster caps are not offered (no cursor under caps):
-    ``news_cluster`` / ``cluster_cap`` are named only to say so, anything but None raises ValueError."""
+    ``news_cluster`` / ``cluster_cap`` are named only to say so, anything but None raises ValueError;
+    so is ``interest_cap``. ``return_interest`` (per page, as in rank_topk) adds interests [U,topk]
+    int32 as a third result."""
     if news_cluster is not None or cluster_cap is not None:
         raise ValueError("rank_topk_deep pages with cursors, and there is no cursor under news_cluster / cluster_cap")
+    if interest_cap is not None:
+        raise ValueError("rank_topk_deep pages with cursors, and there is no cursor under interest_cap")
+    _interest_args(None, return_interest, score_type)
     if isinstance(topk, bool) or not isinstance(topk, int) or topk < 1:
         raise ValueError("topk must be an int >= 1")
     U, N = user_mui.shape[0], news.shape[0]
@@ -453,14 +519,17 @@ def rank_topk_deep(user_mui: Tensor, user_proj: Optional[Tensor], news: Tensor, 
     dev = user_mui.device
     top_s = torch.empty(U, topk, dtype=torch.float32, device=dev)
     top_i = torch.empty(U, topk, dtype=torch.int32, device=dev)
+    top_g = torch.empty(U, topk, dtype=torch.int32, device=dev) if return_interest else None
     for k0 in range(0, topk, MAX_TOPK):
         k1 = min(topk, k0 + MAX_TOPK)
         page = rank_topk(user_mui, user_proj, news, k1 - k0, score_type=score_type, exclude_ids=exclude_ids,
-                         eligible=ok, news_ids=sub, news_bias=pri, after=cur)
-        top_s[:, k0:k1], top_i[:, k0:k1] = page
+                         eligible=ok, news_ids=sub, news_bias=pri, after=cur, return_interest=return_interest)
+        top_s[:, k0:k1], top_i[:, k0:k1] = page[:2]
+        if return_interest:
+            top_g[:, k0:k1] = page[2]
         if k1 < topk:
-            cur = _Cursor(*page_cursor(page))
-    return top_s, top_i
+            cur = _Cursor(*page_cursor(page[:2]))
+    return (top_s, top_i, top_g) if return_interest else (top_s, top_i)
 
 
 def _list_pair(lists, what: str):
@@ -476,8 +545,23 @@ def _list_pair(lists, what: str):
     return _contig(s, torch.float32), _contig(i, torch.int32)
 
 
+def _is_triple(lists) -> bool:
+    return isinstance(lists, (tuple, list)) and len(lists) == 3
+
+
+def _list_triple(lists, what: str):
+    """(scores, ids, interests) -> the checked pair plus the interests int32 [U,k]."""
+    g = lists[2]
+    if not isinstance(g, Tensor) or not isinstance(lists[0], Tensor) or g.shape != lists[0].shape \
+            or g.is_floating_point() or g.is_complex() or g.dtype == torch.bool:
+        raise ValueError(f"{what}: integer interests of the lists' shape [U,k]")
+    s, i = _list_pair(lists[:2], what)
+    _require_device(g)
+    return s, i, _contig(g, torch.int32)
+
+
 def merge_topk(a, b, topk: Optional[int] = None, *, eligible: Optional[Tensor] = None, news_cluster=None,
-               cluster_cap: Optional[int] = None):
+               cluster_cap: Optional[int] = None, interest_cap: Optional[int] = None):
     """Merge two per-user top-k lists (scores [U,k] fp32, ids [U,k] integer; k <= 256 each) on the
     device under the ranker's order (score descending, then lower news id): the best ``topk``
     (default: the wider list's k) of their union, then the (-inf, -1) tail. A news in both lists
@@ -488,10 +572,31 @@ def merge_topk(a, b, topk: Optional[int] = None, *, eligible: Optional[Tensor] =
     ``news_cluster`` / ``cluster_cap`` (as in rank_topk; the table may be any length >= 1, an id at or
     past it is in no cluster): after the replacement and the pruning, the capped walk over what is
     left — the inputs need not be capped. Capped lists merge as top-k lists do: for disjoint A and
-    B, merge_topk(capped(A), capped(B), caps) is capped(A ∪ B), bit for bit."""
+    B, merge_topk(capped(A), capped(B), caps) is capped(A ∪ B), bit for bit.
+    With (scores, ids, interests) triples (rank_topk's ``return_interest``) the result is a triple:
+    every entry carries its interest along (b's entry keeps b's), and ``interest_cap`` (an int in
+    [1, 256]) runs the capped walk with the entry's own interest as its group — for disjoint A and B
+    the interest-capped lists of one user merge to the interest-capped ranking of A ∪ B, bit for
+    bit. A pair mixed with a triple, ``interest_cap`` with pairs, and ``interest_cap`` or triples
+    together with news_cluster / cluster_cap raise ValueError."""
+    triple = _is_triple(a)
+    if triple != _is_triple(b):
+        raise ValueError("merge_topk: both lists are (scores, ids) pairs or both (scores, ids, interests) triples")
+    if interest_cap is not None:
+        if isinstance(interest_cap, bool) or not isinstance(interest_cap, int) or not 1 <= interest_cap <= MAX_TOPK:
+            raise ValueError(f"interest_cap must be an int in [1, {MAX_TOPK}]")
+        if not triple:
+            raise ValueError("interest_cap needs (scores, ids, interests) triples")
+    if triple and (news_cluster is not None or cluster_cap is not None):
+        raise ValueError("lists with interests cannot be merged under news_cluster / cluster_cap")
     caps = _caps(news_cluster, cluster_cap, None)
-    a_s, a_i = _list_pair(a, "list a")
-    b_s, b_i = _list_pair(b, "list b")
+    a_g = b_g = None
+    if triple:
+        a_s, a_i, a_g = _list_triple(a, "list a")
+        b_s, b_i, b_g = _list_triple(b, "list b")
+    else:
+        a_s, a_i = _list_pair(a, "list a")
+        b_s, b_i = _list_pair(b, "list b")
     U, ka = a_s.shape
     kb = b_s.shape[1]
     if b_s.shape[0] != U:
@@ -513,6 +618,15 @@ def merge_topk(a, b, topk: Optional[int] = None, *, eligible: Optional[Tensor] =
     dev = a_s.device
     out_s = torch.empty(U, topk, dtype=torch.float32, device=dev)
     out_i = torch.empty(U, topk, dtype=torch.int32, device=dev)
+    if triple:
+        out_g = torch.empty(U, topk, dtype=torch.int32, device=dev)
+        with torch.cuda.device(dev):
+            rc = _lib.lib().miner_topk_merge_grouped(_stream(dev), _ptr(a_s) if ka else None, _ptr(a_i) if ka else None, ka,
+                                                     _ptr(b_s) if kb else None, _ptr(b_i) if kb else None, kb, U, topk,
+                                                     _ptr(ok), N, _ptr(out_s), _ptr(out_i), _ptr(a_g) if ka else None,
+                                                     _ptr(b_g) if kb else None, _ptr(out_g), interest_cap or 0)
+        _lib.check(rc, "miner_topk_merge_grouped")
+        return out_s, out_i, out_g
     with torch.cuda.device(dev):
         rc = _lib.lib().miner_topk_merge_capped(_stream(dev), _ptr(a_s) if ka else None, _ptr(a_i) if ka else None, ka,
                                                 _ptr(b_s) if kb else None, _ptr(b_i) if kb else None, kb, U, topk,
@@ -526,7 +640,7 @@ def merge_topk(a, b, topk: Optional[int] = None, *, eligible: Optional[Tensor] =
 def update_topk(lists, user_mui: Tensor, user_proj: Optional[Tensor], news: Tensor, news_ids, *,
                 score_type: str = "weighted", exclude_ids: Optional[Tensor] = None,
                 eligible: Optional[Tensor] = None, news_bias=None, user_group: Optional[Tensor] = None,
-                news_cluster=None, cluster_cap: Optional[int] = None):
+                news_cluster=None, cluster_cap: Optional[int] = None, interest_cap: Optional[int] = None):
     """Incremental ranking: ``lists`` = (scores [U,k], ids [U,k]) ranked earlier for these users; the
     table rows ``news_ids`` (new or changed news) are ranked with rank_topk(news_ids=...) and merged
     in with merge_topk — a re-ranked news takes its fresh score. ``exclude_ids`` filters the fresh
@@ -541,17 +655,35 @@ def update_topk(lists, user_mui: Tensor, user_proj: Optional[Tensor], news: Tens
     list holds only what its caps let through, so when ``eligible`` prunes an entry, or a re-ranked
     news comes back with a lower score, the same-cluster news that entry once displaced is no longer
     in the list and does not return — the result is within its caps, but may miss that news until
-    the users are ranked again."""
+    the users are ranked again.
+    ``lists`` may be a (scores, ids, interests) triple (rank_topk's ``return_interest``): the fresh
+    rows are ranked with their interests and the result is a triple. ``interest_cap`` (triples only;
+    not with news_cluster / cluster_cap) as in rank_topk: the fresh rows are ranked under the
+    per-interest cap and merged with the grouped merge. Exact and stale exactly as under the
+    per-cluster caps: where the fresh ids are new to ``lists`` and ``lists`` is the interest-capped
+    ranking of the old ids for the same user vectors, the result is the interest-capped ranking of
+    the union, bit for bit; but a capped list holds only what its caps let through, so when
+    ``eligible`` prunes an entry, or a re-ranked news comes back with a lower score, the
+    same-interest news that entry once displaced is no longer in the list and does not return —
+    within its caps, but possibly missing that news until the users are ranked again. (And the
+    interests in ``lists`` are those of the user vectors it was ranked with.)"""
+    triple = _is_triple(lists)
+    icap = _interest_args(interest_cap, triple, score_type, news_cluster, cluster_cap)
+    if icap and not triple:
+        raise ValueError("interest_cap needs lists with interests: a (scores, ids, interests) triple")
+    if triple and (news_cluster is not None or cluster_cap is not None):
+        raise ValueError("lists with interests cannot be updated under news_cluster / cluster_cap")
     pri = _prior(news_bias, user_group, user_mui.shape[0], news.shape[0])
     caps = _caps(news_cluster, cluster_cap, news.shape[0])
-    old = _list_pair(lists, "lists")
+    old = _list_triple(lists, "lists") if triple else _list_pair(lists, "lists")
     k = old[0].shape[1]
     if k < 1:
         raise ValueError("lists must hold at least one entry per user")
     ok = None if eligible is None else _eligible_words(eligible, news.shape[0])
     fresh = rank_topk(user_mui, user_proj, news, k, score_type=score_type, exclude_ids=exclude_ids, eligible=ok,
-                      news_ids=news_ids, news_bias=pri, news_cluster=caps)
-    return merge_topk(old, fresh, k, eligible=ok, news_cluster=caps)
+                      news_ids=news_ids, news_bias=pri, news_cluster=caps, interest_cap=interest_cap,
+                      return_interest=triple)
+    return merge_topk(old, fresh, k, eligible=ok, news_cluster=caps, interest_cap=interest_cap)
 
 
 def cap_topk(lists, news_cluster, cluster_cap: int, topk: Optional[int] = None):
@@ -611,32 +743,42 @@ def _bits_at(words: Tensor, ids: Tensor) -> Tensor:
     return (((words[safe >> 5].to(torch.int64) >> (safe & 31)) & 1) != 0) & (ids >= 0)
 
 
-def _score_pairs(st, dt, mui, proj, tab, ids64: Tensor, pri: Optional[_Prior] = None) -> Tensor:
+def _score_pairs(st, dt, mui, proj, tab, ids64: Tensor, pri: Optional[_Prior] = None, interest: bool = False):
+    """scores [U, C]; with ``interest`` (scores, interests int32 [U, C]) from the one launch."""
     U, K, d = mui.shape
     C = ids64.shape[1]
     out = torch.empty(U, C, dtype=torch.float32, device=mui.device)
+    intr = torch.empty(U, C, dtype=torch.int32, device=mui.device) if interest else None
     if U == 0 or C == 0:
-        return out
+        return (out, intr) if interest else out
     ids = ids64.to(torch.int32).contiguous()
     with torch.cuda.device(mui.device):
-        rc = _lib.lib().miner_score_pairs_biased(_stream(mui.device), dt, st, _ptr(mui), _ptr(proj), _ptr(tab), U,
-                                                 tab.shape[0], d, K, _ptr(ids), C, _ptr(out), *_prior_args(pri))
+        rc = _lib.lib().miner_score_pairs_interest(_stream(mui.device), dt, st, _ptr(mui), _ptr(proj), _ptr(tab), U,
+                                                   tab.shape[0], d, K, _ptr(ids), C, _ptr(out), *_prior_args(pri),
+                                                   _ptr(intr))
     _lib.check(rc, "miner_score_pairs")
-    return out
+    return (out, intr) if interest else out
 
 
 def score_pairs(user_mui: Tensor, user_proj: Optional[Tensor], news: Tensor, cand_ids: Tensor, *,
-                score_type: str = "weighted", news_bias=None, user_group: Optional[Tensor] = None) -> Tensor:
+                score_type: str = "weighted", news_bias=None, user_group: Optional[Tensor] = None,
+                return_interest: bool = False):
     """The click score of chosen pairs: scores[u, c] of (user u, news[cand_ids[u, c]]), fp32 [U, C] —
     bit for bit what rank_topk computes for that pair, from the cached user vectors. cand_ids [U, C]
     of any integer dtype, any order, repeats allowed; an id outside [0, N) (a -1 padding) gives -inf.
     Only the U x C rows are read: the second stage of a recommender, or the refresh of a served list
     (rescore_topk). ``news_bias`` / ``user_group`` as in rank_topk: the prior of the pair's news is
-    added (an id outside [0, N) stays -inf)."""
+    added (an id outside [0, N) stays -inf). ``return_interest``: (scores, interests) — interests
+    int32 [U, C], the dominant interest of each pair (rank_topk's ``return_interest``: the lowest k
+    whose logit, or M_k under 'max', equals the maximum the score's reduction over K found; -1 for
+    an id outside [0, N); ValueError under 'mean'), from the same launch: the scores keep their bits
+    and the prior does not enter the interest."""
+    _interest_args(None, return_interest, score_type)
     _check_ids(cand_ids, user_mui.shape[0], "cand_ids")
     pri = _prior(news_bias, user_group, user_mui.shape[0], news.shape[0])
     st, dt, mui, proj, tab = _rank_operands(user_mui, user_proj, news, score_type)
-    return _score_pairs(st, dt, mui, proj, tab, _id_matrix(cand_ids, mui.shape[0], tab.shape[0], "cand_ids"), pri)
+    return _score_pairs(st, dt, mui, proj, tab, _id_matrix(cand_ids, mui.shape[0], tab.shape[0], "cand_ids"), pri,
+                        return_interest)
 
 
 def _better(s: Tensor, i: Tensor, s2: Tensor, i2: Tensor) -> Tensor:
@@ -829,7 +971,7 @@ def rank_corpus(news: Tensor, his_ids: Tensor, his_mask: Tensor, packed: Encoder
                 out: Optional[tuple] = None, exclude_history: bool = False, exclude_ids: Optional[Tensor] = None,
                 eligible: Optional[Tensor] = None, news_ids=None, news_bias=None,
                 user_group: Optional[Tensor] = None, news_cluster=None, cluster_cap: Optional[int] = None,
-                after=None):
+                after=None, interest_cap: Optional[int] = None, return_interest: bool = False):
     """BASELINE config 5 on one GPU's share of the users: every user (his_ids [U,L] into the news
     table [N,d], his_mask [U,L]) encoded and ranked against the whole table, ``batch`` users per
     encode + rank pair so that the [batch,K,d] user vectors are all that is ever held (125,000 users
@@ -841,11 +983,17 @@ def rank_corpus(news: Tensor, his_ids: Tensor, his_mask: Tensor, packed: Encoder
     ``exclude_ids`` [U,E] further ids, together at most 256 per user; ``eligible`` and ``news_ids`` (rank only these table rows) as in
     rank_topk; ``news_bias`` / ``user_group`` [U] (a score prior, checked once and sliced per batch) too;
     ``news_cluster`` / ``cluster_cap`` (per-cluster caps, checked and converted once) too; ``after``
-    (keyset cursors [U], checked once and sliced per batch; never together with the caps) too."""
+    (keyset cursors [U], checked once and sliced per batch; never together with the caps) too;
+    ``interest_cap`` / ``return_interest`` (per-interest caps and the listed pairs' dominant interests,
+    as in rank_topk) too: with ``return_interest`` the result, and ``out``, is a (scores, ids,
+    interests [U,topk] int32) triple."""
     if batch <= 0:
         raise ValueError("batch must be positive")
     U = his_ids.shape[0]
     dev = news.device
+    _interest_args(interest_cap, return_interest, score_type, news_cluster, cluster_cap, after)
+    if out is not None and len(out) != (3 if return_interest else 2):
+        raise ValueError("out must be (scores, ids), or (scores, ids, interests) with return_interest")
     _no_cursor_under_caps(after, news_cluster, cluster_cap)
     pri = _prior(news_bias, user_group, U, news.shape[0])
     caps = _caps(news_cluster, cluster_cap, news.shape[0])
@@ -854,17 +1002,19 @@ def rank_corpus(news: Tensor, his_ids: Tensor, his_mask: Tensor, packed: Encoder
     excl = _exclusions(exclude_ids, exclude_history, his_ids, his_mask)
     ok = None if eligible is None else _eligible_words(eligible, news.shape[0])   # packed once
     sub = None if news_ids is None else _news_id_list(news_ids, news.shape[0])    # canonicalised once
-    top_s, top_i = out if out is not None else (torch.empty(U, topk, dtype=torch.float32, device=dev),
-                                                torch.empty(U, topk, dtype=torch.int32, device=dev))
+    res = tuple(out) if out is not None else (torch.empty(U, topk, dtype=torch.float32, device=dev),
+                                              torch.empty(U, topk, dtype=torch.int32, device=dev)) + \
+        ((torch.empty(U, topk, dtype=torch.int32, device=dev),) if return_interest else ())
     with_proj = score_type == "weighted"
     for u0 in range(0, U, batch):
         u1 = min(U, u0 + batch)
         mui, proj = encode_users(news, his_mask[u0:u1], packed, his_ids=his_ids[u0:u1],
                                  his_bias=None if his_bias is None else his_bias[u0:u1], with_proj=with_proj)
-        s, i = rank_topk(mui, proj, news, topk, score_type=score_type,
-                         exclude_ids=None if excl is None else excl[u0:u1], eligible=ok, news_ids=sub,
-                         news_bias=None if pri is None else pri.users(u0, u1), news_cluster=caps,
-                         after=None if cur is None else cur.users(u0, u1))
-        top_s[u0:u1] = s
-        top_i[u0:u1] = i
-    return top_s, top_i
+        got = rank_topk(mui, proj, news, topk, score_type=score_type,
+                        exclude_ids=None if excl is None else excl[u0:u1], eligible=ok, news_ids=sub,
+                        news_bias=None if pri is None else pri.users(u0, u1), news_cluster=caps,
+                        after=None if cur is None else cur.users(u0, u1), interest_cap=interest_cap,
+                        return_interest=return_interest)
+        for dst, src in zip(res, got):
+            dst[u0:u1] = src
+    return res

@@ -466,6 +466,9 @@ struct RkParams {
   int cap;                 //      of one cluster
   const float* aft_s;      // AFT: the keyset cursors [U] (NULL: none); user u's list holds only what ranks
   const int32_t* aft_i;    //      strictly after (aft_s[u], aft_i[u])
+  int32_t* top_g;          // INT: the dominant interests out — pair form [U][M] next to the scores; capped form
+  int icap;                //      [U][topk] next to the list (NULL: not wanted). icap > 0: the per-interest cap
+                           //      as the caller gave it; the kernel reads it as `cap` (rk_run), as the capped form does
 };
 
 // S > 1 (S = 8, grid = 256): the news steps are dealt to S slices (step st of slice s is news step
@@ -539,7 +542,7 @@ __device__ __forceinline__ unsigned rk_okey(float s) {
 }
 __device__ __forceinline__ unsigned rk_ikey(int id) { return (unsigned)id ^ 0x7fffffffu; }
 
-template <int NR, int GEO = 0, bool FLT = false, bool CAP = false>
+template <int NR, int GEO = 0, bool FLT = false, bool CAP = false, bool INT = false>
 struct RkLds {
   static constexpr int kARows = kUT * NR * 32;
   static constexpr int kStage = (kARows + kNT) * kRB<GEO>;
@@ -548,9 +551,10 @@ struct RkLds {
   static constexpr int kOffCnt = kOffStage + 2 * kUT * kNT * 8;     // list counts [kUT], staged [2][kUT]
   static constexpr int kOffExcl = kOffCnt + 64;                     // the tile's exclusion lists [kUT][kMaxL] int
   // CAP: per list entry its cluster id and its rank inside its cluster, [kUT][kMaxTopk] int each,
-  // then the cluster ids of the staged entries being merged [kUT][kNT]
+  // then the cluster ids of the staged entries being merged [kUT][kNT] (INT: the interests staged with
+  // the entries by the epilogue, double buffered as the staging area is, [2 bufs][kUT][kNT])
   static constexpr int kOffClus = kOffExcl + (FLT ? kUT * kMaxL * 4 : 0);
-  static constexpr int kTotal = kOffClus + (CAP ? (2 * kUT * kMaxTopk + kUT * kNT) * 4 : 0);
+  static constexpr int kTotal = kOffClus + (CAP ? (2 * kUT * kMaxTopk + (INT ? 2 : 1) * kUT * kNT) * 4 : 0);
 };
 
 // NCH: RB-byte d-chunks per row (0: at run time); GEO: the stream geometry (kRB / kRing); FLT: the
@@ -596,6 +600,19 @@ struct RkLds {
 // its bits. To keep the build small the CAP instantiations are the BIAS ones with the prior tested at
 // run time (no table: nothing is loaded and nothing is added, so an unbiased capped score is not
 // "score + 0"); CAP is a compile-time switch so that every other instantiation is the code it was.
+// INT: the interest forms (RkParams top_g / icap). interest(u, n) is the lowest k in [0, K) whose value
+// equals the maximum the score's own K reduction found — over the logits proj_k · e_n ('weighted': the
+// mx of the softmax) or over M_k ('max': the score itself) —, -1 if none compares equal (all NaN). It
+// is read off the accumulators the score was made from, after the contraction (rk_interest), so no
+// score bit changes, and a prior never enters it. Accumulator e of lane half h in interest tile kt
+// is interest 32 kt + 16 h + e (the row of the user image that lane pi_row⁻¹ loaded: pi_row(acc_row(e,
+// h)) = 16 h + e), the index the K mask of the epilogue uses. kPair | INT: the interest is stored
+// next to the score, top_g[u][pos] (-1 for an id outside [0, N)). CAP | INT: the capped form with the
+// group of an entry its interest instead of clus[id]: computed lazily, only by the half-waves that
+// stage something (bal != 0; the accumulators are still live there), staged with the entry (stg_g,
+// double buffered) and read by the capped merge in place of its table loads; the list's groups leave
+// with the list (top_g, when wanted). Never for the mean score, which has no dominant interest (the
+// INT forms are not instantiated for it).
 constexpr int kRank = 0, kCount = 1, kPair = 2;
 constexpr int kMaxT = MINER_CORPUS_MAX_TARGETS;
 
@@ -610,26 +627,50 @@ __device__ __forceinline__ float rk_add_rn(float a, float b) {
 // above as named bits, kCount / kPair for MODE (neither: kRank), kFSplit for S = kSplit, and the
 // shape bits of the launcher (kFD768: NCH = 768 · 2 / RB, kFK64: KC = 64; 0 is "at run time").
 constexpr unsigned kFFlt = 1, kFSub = 2, kFBias = 4, kFCap = 8, kFAft = 16, kFGeo1 = 32, kFSplit = 64, kFCount = 128,
-                   kFPair = 256, kFD768 = 512, kFK64 = 1024;
+                   kFPair = 256, kFD768 = 512, kFK64 = 1024, kFInt = 2048;
 template <unsigned F>
 struct RkForm {
   static constexpr bool FLT = F & kFFlt, SUB = F & kFSub, BIAS = F & kFBias, CAP = F & kFCap, AFT = F & kFAft;
+  static constexpr bool INT = F & kFInt;
   static constexpr int MODE = F & kFCount ? kCount : F & kFPair ? kPair : kRank;
   static constexpr int S = F & kFSplit ? kSplit : 1, GEO = F & kFGeo1 ? 1 : 0;
   static constexpr int NCH = F & kFD768 ? 768 * 2 / kRB<GEO> : 0, KC = F & kFK64 ? 64 : 0;   // KC: K compile-time (0: run time)
-  static_assert(F < 2 * kFK64 && (F & (kFCount | kFPair)) != (kFCount | kFPair) && (!(F & kFK64) || (F & kFD768)), "a form");
+  static_assert(F < 2 * kFInt && (F & (kFCount | kFPair)) != (kFCount | kFPair) && (!(F & kFK64) || (F & kFD768)), "a form");
   static_assert(!AFT || (MODE == kRank && GEO == 0 && FLT && BIAS && !CAP), "the cursor form: filtered, on the biased form, uncapped");
   static_assert(!CAP || (MODE == kRank && S == 1 && GEO == 0 && FLT && BIAS), "the capped form: unsplit, filtered, on the biased form");
+  static_assert(!INT || MODE == kPair || CAP, "the interest forms: the pair form and the capped form");
   static_assert(!SUB || (FLT && GEO == 0), "the subset form: a filtered form with one chunk in flight");
   static_assert(!BIAS || (GEO == 0 && (FLT || MODE == kCount)), "the biased forms: GEO 0, the ranking forms filtered");
   static_assert(MODE == kRank || (S == 1 && GEO == 0 && SUB == (MODE == kPair)), "counting and pair forms: unsplit, GEO 0");
 };
 
+// INT: the dominant interest of this lane's news from the NKT accumulator tiles lg[0 .. NKT) the K
+// reduction ran over and the maximum mx it found (the same in both lane halves): per lane the lowest
+// k of its half's elements that compare equal to mx (walked downwards, so the last hit is the
+// lowest), then the lane-half exchange the maximum made, taking the lower; -1 if no element compares
+// equal. All 64 lanes take part.
+constexpr int kNoInterest = 0x7fffffff;
+template <int NKT>
+__device__ __forceinline__ int rk_interest(const f32x16 (*lg)[2], int nt, float mx, int h, int K) {
+  int kk = kNoInterest;
+#pragma unroll
+  for (int kt = NKT - 1; kt >= 0; --kt)
+#pragma unroll
+    for (int e = 15; e >= 0; --e) {
+      const int k = 32 * kt + 16 * h + e;
+      if (k < K && lg[kt][nt][e] == mx) kk = k;
+    }
+  const auto s = __builtin_amdgcn_permlane32_swap((unsigned)kk, (unsigned)kk, false, false);
+  kk = min((int)s[0], (int)s[1]);
+  return kk == kNoInterest ? -1 : kk;
+}
+
 template <class T, int NKT, int SCORE, unsigned F>
 __global__ __launch_bounds__(kThreads) void rk_fused(RkParams p) {
   using Fm = RkForm<F>;
   constexpr int NCH = Fm::NCH, S = Fm::S, GEO = Fm::GEO, KC = Fm::KC, MODE = Fm::MODE;
-  constexpr bool FLT = Fm::FLT, SUB = Fm::SUB, BIAS = Fm::BIAS, CAP = Fm::CAP, AFT = Fm::AFT;
+  constexpr bool FLT = Fm::FLT, SUB = Fm::SUB, BIAS = Fm::BIAS, CAP = Fm::CAP, AFT = Fm::AFT, INT = Fm::INT;
+  static_assert(!INT || SCORE != MINER_SCORE_MEAN, "the mean score has no dominant interest");
   static_assert((NCH == 0 || sizeof(T) == 2) && (KC == 0 || NKT == 2), "the compile-time shape: 16-bit, K = 64 on two interest tiles");
   constexpr bool kRtPrior = CAP || AFT;             // BIAS instantiations that test the prior at run time
   static_assert(kMaxT == 64 && kUT * kMaxT * 8 <= kUT * kMaxTopk * 8 && kUT * 4 * kMaxT * 4 <= 2 * kUT * kNT * 8,
@@ -638,7 +679,7 @@ __global__ __launch_bounds__(kThreads) void rk_fused(RkParams p) {
   constexpr bool kW = SCORE == MINER_SCORE_WEIGHTED;
   constexpr int NR = kW ? 2 * NKT : NKT;            // row tiles per user: mui (and proj)
   constexpr int RB = kRB<GEO>, RING = kRing<GEO>, PD = RING - 1;   // PD: chunks in flight
-  using LD = RkLds<NR, GEO, FLT, CAP>;
+  using LD = RkLds<NR, GEO, FLT, CAP, INT>;
   constexpr int kChunkSlabs = RB / (32 * (int)sizeof(T));          // 32-index slabs per chunk
   static_assert(kChunkSlabs >= 1, "a chunk holds whole slabs");
   const int d = NCH > 0 ? NCH * RB / (int)sizeof(T) : p.d, K = KC > 0 ? KC : p.K, N = p.N;
@@ -656,7 +697,7 @@ __global__ __launch_bounds__(kThreads) void rk_fused(RkParams p) {
   int* excl = reinterpret_cast<int*>(smem + LD::kOffExcl);  // [kUT][kMaxL], -1 past E (FLT and p.E > 0 only)
   [[maybe_unused]] int* list_g = reinterpret_cast<int*>(smem + LD::kOffClus);                   // CAP: [kUT][kMaxTopk]
   [[maybe_unused]] int* list_r = reinterpret_cast<int*>(smem + LD::kOffClus + kUT * kMaxTopk * 4);
-  [[maybe_unused]] int* stg_g = reinterpret_cast<int*>(smem + LD::kOffClus + 2 * kUT * kMaxTopk * 4);   // [kUT][kNT]
+  [[maybe_unused]] int* stg_g = reinterpret_cast<int*>(smem + LD::kOffClus + 2 * kUT * kMaxTopk * 4);   // [kUT][kNT]; INT: [buf][kUT][kNT]
   // counting form (no list, nothing staged): the targets [kUT][kMaxT] and the waves' partial counts [kWaves][kMaxT]
   [[maybe_unused]] unsigned* tg_h = reinterpret_cast<unsigned*>(smem + LD::kOffList);   // key halves: score, id
   [[maybe_unused]] unsigned* tg_l = reinterpret_cast<unsigned*>(smem + LD::kOffList + kUT * kMaxT * 4);
@@ -802,14 +843,17 @@ __global__ __launch_bounds__(kThreads) void rk_fused(RkParams p) {
       // wave that staged something.
       int* lg_ = list_g + uu * kMaxTopk;
       int* lrk_ = list_r + uu * kMaxTopk;
-      int* mg = stg_g + uu * kNT;
+      // INT: the groups are the interests the epilogue staged with the entries: nothing is loaded
+      // from global memory and the staged array itself is what the walk below reads.
+      int* mg = stg_g + (INT ? buf * kUT + uu : uu) * kNT;
       int sg[kST], lg[kLT], lrc[kLT], src[kST];
 #pragma unroll
       for (int v = 0; v < kST; ++v) {
         const int j = min(lane + 64 * v, kNT - 1);
         sv[v] = ss[j];
         sid[v] = si[j];
-        sg[v] = lane + 64 * v < ns ? p.clus[sid[v]] : -1;   // a staged id is a table row: inside [0, N)
+        if constexpr (INT) sg[v] = lane + 64 * v < ns ? mg[j] : -1;
+        else sg[v] = lane + 64 * v < ns ? p.clus[sid[v]] : -1;   // a staged id is a table row: inside [0, N)
         src[v] = 0;
       }
 #pragma unroll
@@ -821,8 +865,10 @@ __global__ __launch_bounds__(kThreads) void rk_fused(RkParams p) {
         lg[t] = in ? lg_[i] : -1;
         lrc[t] = lrk_[i];
       }
+      if constexpr (!INT) {
 #pragma unroll
-      for (int v = 0; v < kST; ++v) mg[lane + 64 * v] = sg[v];
+        for (int v = 0; v < kST; ++v) mg[lane + 64 * v] = sg[v];
+      }
       for (int j2 = 0; j2 < ns; ++j2) {
         const int g2 = __builtin_amdgcn_readfirstlane(mg[j2]);
         if (g2 < 0) continue;                    // never capped, and in nobody's cluster
@@ -1137,6 +1183,7 @@ __global__ __launch_bounds__(kThreads) void rk_fused(RkParams p) {
           // the candidate's identity: its table row (SUB: of this position's id, -1 for "none")
           const int n = SUB ? nid[nt] : st * kNT + 64 * nsub + 32 * nt + r;
           float score;
+          [[maybe_unused]] float kmx = 0.f;          // INT: the maximum of the K reduction
           if constexpr (kW) {
             // 4 independent max / sum chains per lane (a 32-long dependent chain each otherwise)
             float m4[4] = {-INFINITY, -INFINITY, -INFINITY, -INFINITY};
@@ -1146,6 +1193,7 @@ __global__ __launch_bounds__(kThreads) void rk_fused(RkParams p) {
               for (int e = 0; e < 16; ++e)
                 if (32 * kt + 16 * h + e < K) m4[e & 3] = fmaxf(m4[e & 3], acc[NKT + kt][nt][e]);
             const float mx = xor32_max(fmaxf(fmaxf(m4[0], m4[1]), fmaxf(m4[2], m4[3])));
+            kmx = mx;
             float s0[4] = {0.f, 0.f, 0.f, 0.f}, s1[4] = {0.f, 0.f, 0.f, 0.f};
             // 16-bit: exp(x - mx) as exp2(x·log2 e - mx·log2 e), one fma + v_exp_f32 per interest
             const float mxl = mx * 1.44269504088896340736f;
@@ -1170,6 +1218,7 @@ __global__ __launch_bounds__(kThreads) void rk_fused(RkParams p) {
               for (int e = 0; e < 16; ++e)
                 if (32 * kt + 16 * h + e < K) mx = fmaxf(mx, acc[kt][nt][e]);
             score = xor32_max(mx);                       // model.py:128-129
+            kmx = score;
           } else {
             float sm = 0.f;
 #pragma unroll
@@ -1208,6 +1257,10 @@ __global__ __launch_bounds__(kThreads) void rk_fused(RkParams p) {
             // both uu halves hold this user's scores: the first stores (n < 0: an id outside [0, N))
             const int pos = st * kNT + 64 * nsub + 32 * nt + r;
             if (uu == 0 && h == 0 && pos < p.M) p.top_s[(size_t)ti * p.M + pos] = n >= 0 ? score : -INFINITY;
+            if constexpr (INT) {
+              const int g = rk_interest<NKT>(acc + (kW ? NKT : 0), nt, kmx, h, K);
+              if (uu == 0 && h == 0 && pos < p.M) p.top_g[(size_t)ti * p.M + pos] = n >= 0 ? g : -1;
+            }
             continue;
           }
           bool cand = h == 0 && (SUB ? n >= 0 : n < N) && user < p.U && better(score, n, th_s, th_i);
@@ -1248,10 +1301,15 @@ __global__ __launch_bounds__(kThreads) void rk_fused(RkParams p) {
             int b0 = 0;
             if (lane == 0) b0 = atomicAdd(&cnt[kUT + buf * kUT + uu], __popcll(bal));
             b0 = __builtin_amdgcn_readfirstlane(b0);
+            // INT: the interests of this half-wave's news, only here where something is staged (bal is
+            // wave-uniform, the accumulators are live, both lane halves take part in the exchange)
+            [[maybe_unused]] int g = -1;
+            if constexpr (INT) g = rk_interest<NKT>(acc + (kW ? NKT : 0), nt, kmx, h, K);
             if (cand) {
               const int slot = b0 + __popcll(bal & ((1ull << lane) - 1));
               stg_s[(buf * kUT + uu) * kNT + slot] = score;
               stg_i[(buf * kUT + uu) * kNT + slot] = n;
+              if constexpr (INT) stg_g[(buf * kUT + uu) * kNT + slot] = g;
             }
           }
         }
@@ -1286,6 +1344,7 @@ __global__ __launch_bounds__(kThreads) void rk_fused(RkParams p) {
           const bool ok = i < cnt[uu];
           ds[o + i] = ok ? list_s[uu * kMaxTopk + i] : -INFINITY;
           di[o + i] = ok ? list_i[uu * kMaxTopk + i] : -1;
+          if constexpr (INT) if (p.top_g != nullptr) p.top_g[o + i] = ok ? list_g[uu * kMaxTopk + i] : -1;
         }
       }
       __syncthreads();
@@ -1362,13 +1421,20 @@ __global__ __launch_bounds__(256) void rk_merge(const float* __restrict__ ws_s, 
 // for it) are loaded after the drop and replace steps; per entry rc = the better entries of its own
 // cluster, kept iff unclustered or rc < cap; an entry's rank = the better KEPT entries; the
 // (-inf, -1) tail follows the kept count.
-template <bool CAP>
+// GM 2, the grouped merge (per-entry groups: the interests of the interest forms): an entry's group
+// comes with it (a_g [U, ka] / b_g [U, kb], < 0: none) instead of from clus[id], so b's entry keeps
+// b's group through the replacement; the kept entries' groups go to out_g [U, topk] (-1 in the
+// tail). cap == 0: no walk, the groups are only carried.
+template <int GM>
 __global__ __launch_bounds__(64 * kMergeUsers) void topk_merge(const float* __restrict__ a_s, const int32_t* __restrict__ a_i,
                                                                int ka, const float* __restrict__ b_s,
                                                                const int32_t* __restrict__ b_i, int kb, int U, int topk,
                                                                const uint32_t* __restrict__ ok, int N,
                                                                float* __restrict__ out_s, int32_t* __restrict__ out_i,
-                                                               const int32_t* __restrict__ clus, int n_clus, int cap) {
+                                                               const int32_t* __restrict__ clus, int n_clus, int cap,
+                                                               const int32_t* __restrict__ a_g, const int32_t* __restrict__ b_g,
+                                                               int32_t* __restrict__ out_g) {
+  constexpr bool CAP = GM != 0, GRP = GM == 2;
   constexpr int kSlots = 2 * kMaxTopk, kPer = kSlots / 64;
   __shared__ float ms[kMergeUsers][kSlots];
   __shared__ int mi[kMergeUsers][kSlots];
@@ -1378,17 +1444,21 @@ __global__ __launch_bounds__(64 * kMergeUsers) void topk_merge(const float* __re
   if (user >= U) return;                   // wave-uniform; no block barrier below
   float sv[kPer];
   int id[kPer];
+  [[maybe_unused]] int eg[GRP ? kPer : 1];     // GRP: the groups the entries came with
 #pragma unroll
   for (int t = 0; t < kPer; ++t) {
     const int e = lane + 64 * t, eb = e - kMaxTopk;
     sv[t] = -INFINITY;
     id[t] = -1;
+    if constexpr (GRP) eg[t] = -1;
     if (e < ka) {
       sv[t] = a_s[(size_t)user * ka + e];
       id[t] = a_i[(size_t)user * ka + e];
+      if constexpr (GRP) eg[t] = max(a_g[(size_t)user * ka + e], -1);
     } else if (eb >= 0 && eb < kb) {
       sv[t] = b_s[(size_t)user * kb + eb];
       id[t] = b_i[(size_t)user * kb + eb];
+      if constexpr (GRP) eg[t] = max(b_g[(size_t)user * kb + eb], -1);
     }
     if (ok != nullptr && id[t] >= 0 && (id[t] >= N || !((ok[id[t] >> 5] >> (id[t] & 31)) & 1u))) id[t] = -1;
     if (id[t] < 0) id[t] = -1;
@@ -1418,13 +1488,14 @@ __global__ __launch_bounds__(64 * kMergeUsers) void topk_merge(const float* __re
     int g[kPer], rc[kPer];
 #pragma unroll
     for (int t = 0; t < kPer; ++t) {
-      g[t] = id[t] >= 0 && id[t] < n_clus ? max(clus[id[t]], -1) : -1;
+      if constexpr (GRP) g[t] = id[t] >= 0 ? eg[t] : -1;
+      else g[t] = id[t] >= 0 && id[t] < n_clus ? max(clus[id[t]], -1) : -1;
       mg[w][lane + 64 * t] = g[t];
       rc[t] = 0;
     }
     __builtin_amdgcn_s_waitcnt(0);
     __builtin_amdgcn_wave_barrier();
-    for (int half = 0; half < 2; ++half) {
+    for (int half = 0; half < 2 && (!GRP || cap > 0); ++half) {
       const int j0 = half * kMaxTopk, j1 = j0 + (half ? kb : ka);
       for (int j = j0; j < j1; ++j) {
         const int i2 = mi[w][j], g2 = mg[w][j];
@@ -1439,7 +1510,7 @@ __global__ __launch_bounds__(64 * kMergeUsers) void topk_merge(const float* __re
     __builtin_amdgcn_wave_barrier();          // every read of the ids comes before the first write
 #pragma unroll
     for (int t = 0; t < kPer; ++t) {
-      if (g[t] >= 0 && rc[t] >= cap) {
+      if (g[t] >= 0 && rc[t] >= cap && (!GRP || cap > 0)) {
         id[t] = -1;
         mi[w][lane + 64 * t] = -1;
       }
@@ -1468,19 +1539,23 @@ __global__ __launch_bounds__(64 * kMergeUsers) void topk_merge(const float* __re
     if (id[t] >= 0 && rank[t] < topk) {
       out_s[(size_t)user * topk + rank[t]] = sv[t];
       out_i[(size_t)user * topk + rank[t]] = id[t];
+      if constexpr (GRP) out_g[(size_t)user * topk + rank[t]] = eg[t];
     }
   }
   for (int i = min(V, topk) + lane; i < topk; i += 64) {
     out_s[(size_t)user * topk + i] = -INFINITY;
     out_i[(size_t)user * topk + i] = -1;
+    if constexpr (GRP) out_g[(size_t)user * topk + i] = -1;
   }
 }
 
 // every list empty: (-inf, -1) (the subset form with an empty id list)
-__global__ __launch_bounds__(256) void rk_fill_empty(float* __restrict__ top_s, int32_t* __restrict__ top_i, size_t n) {
+__global__ __launch_bounds__(256) void rk_fill_empty(float* __restrict__ top_s, int32_t* __restrict__ top_i,
+                                                     int32_t* __restrict__ top_g, size_t n) {
   for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
     top_s[i] = -INFINITY;
     top_i[i] = -1;
+    if (top_g != nullptr) top_g[i] = -1;
   }
 }
 
@@ -1538,6 +1613,8 @@ constexpr unsigned kRkForms[] = {
     kFSplit, kFSplit | kFFlt, kFSplit | kFSubset, kFSplit | kFBiased, kFSplit | kFBiased | kFSub, kFSplit | kFCursor,
     kFSplit | kFCursor | kFSub,
     kFCapped, kFCapped | kFSub, kFCount, kFCount | kFBias, kFPairs, kFPairs | kFBias,
+    // the interest forms (never instantiated for the mean score: rk_pick)
+    kFPairs | kFInt, kFPairs | kFBias | kFInt, kFCapped | kFInt, kFCapped | kFSub | kFInt,
 #ifdef MINER_RK_GEO1
     kFGeo1, kFGeo1 | kFFlt, kFGeo1 | kFSplit, kFGeo1 | kFSplit | kFFlt,
 #endif
@@ -1547,11 +1624,14 @@ unsigned rk_form(const RkParams& prm, int mode, [[maybe_unused]] int dtype) {
   // the counting and pair forms: unsplit, GEO 0; the biased instantiation only when a prior table
   // was given (the unbiased calls launch what they did)
   if (mode == kCount) return kFCount | (prm.bias != nullptr ? kFBias : 0);
-  if (mode == kPair) return kFPairs | (prm.bias != nullptr ? kFBias : 0);
+  // (the interest instantiation only when the interests were asked for)
+  if (mode == kPair) return kFPairs | (prm.bias != nullptr ? kFBias : 0) | (prm.top_g != nullptr ? kFInt : 0);
   // the id list: one instantiation per shape of every form below, table or subset
   const unsigned sub = prm.ids != nullptr ? kFSub : 0;
   // the capped form — two kernels per shape (table / subset), not four. A workspace is never written.
   if (prm.clus != nullptr) return kFCapped | sub;
+  // the interest-capped form: the capped form with the group taken from the epilogue
+  if (prm.icap > 0) return kFCapped | kFInt | sub;
   const unsigned split = rk_split(prm) ? kFSplit : 0;
   if (prm.aft_s != nullptr) return kFCursor | sub | split;
   if (prm.bias != nullptr) return kFBiased | sub | split;
@@ -1584,7 +1664,7 @@ int rk_launch(void* stream, const RkParams& prm) {
         if (prm.K == 64) kern = rk_fused<T, NKT, SCORE, F | kFD768 | kFK64>;
     }
   }
-  constexpr int lds = RkLds<NR, Fm::GEO, Fm::FLT, Fm::CAP>::kTotal;
+  constexpr int lds = RkLds<NR, Fm::GEO, Fm::FLT, Fm::CAP, Fm::INT>::kTotal;
   static_assert(lds <= 160 * 1024, "ranker LDS (with the exclusion lists and the cluster ids of the form)");
   hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
   if (e != hipSuccess) return (int)e;
@@ -1602,11 +1682,19 @@ int rk_launch(void* stream, const RkParams& prm) {
   return e == hipSuccess ? MINER_OK : (int)e;
 }
 
+// (the mean score has no dominant interest: its interest forms do not exist, and the entry points
+// have answered MINER_EINVAL before anything gets here)
+template <class T, int NKT, int SCORE, unsigned F>
+int rk_launch_form(void* stream, const RkParams& prm) {
+  if constexpr (SCORE == MINER_SCORE_MEAN && (F & kFInt) != 0) return MINER_EINVAL;
+  else return rk_launch<T, NKT, SCORE, F>(stream, prm);
+}
+
 // the one ladder, for every mode: dtype, K <= 32 (one interest tile), score type, then the table
 template <class T, int NKT, int SCORE, size_t... I>
 int rk_pick(void* stream, const RkParams& prm, unsigned form, std::index_sequence<I...>) {
   int rc = MINER_EINVAL;
-  (void)((form == kRkForms[I] && ((rc = rk_launch<T, NKT, SCORE, kRkForms[I]>(stream, prm)), true)) || ...);
+  (void)((form == kRkForms[I] && ((rc = rk_launch_form<T, NKT, SCORE, kRkForms[I]>(stream, prm)), true)) || ...);
   return rc;
 }
 template <class T, int NKT>
@@ -1692,12 +1780,20 @@ int rk_run(void* stream, int dtype, RkParams prm, void* workspace, size_t worksp
   if ((prm.aft_s == nullptr) != (prm.aft_i == nullptr)) return MINER_EINVAL;
   if (prm.aft_s != nullptr && prm.clus != nullptr) return MINER_EINVAL;
   if (!aligned4(prm.aft_s) || !aligned4(prm.aft_i)) return MINER_EALIGN;
+  // the per-interest cap: the capped form's restrictions (no cluster table beside it, no cursor), a
+  // score type that has a dominant interest, and the interests out only under a cap
+  if (prm.icap < 0) return MINER_EINVAL;
+  if (prm.icap > kMaxTopk) return MINER_ESHAPE;
+  if (prm.icap > 0 && (prm.clus != nullptr || prm.aft_s != nullptr)) return MINER_EINVAL;
+  if (prm.icap > 0 && prm.score_type == MINER_SCORE_MEAN) return MINER_EINVAL;
+  if (prm.icap == 0 && prm.top_g != nullptr) return MINER_EINVAL;
+  if (!aligned4(prm.top_g)) return MINER_EALIGN;
   if (prm.U == 0) return MINER_OK;
   if (!aligned16(workspace)) return MINER_EALIGN;
   if (subset && prm.M == 0) {              // nothing to rank: every list empty, no ranker launch
     const size_t n = (size_t)prm.U * prm.topk;
     hipLaunchKernelGGL(rk_fill_empty, dim3((unsigned)((n + 255) / 256 < 1024 ? (n + 255) / 256 : 1024)), dim3(256), 0,
-                       static_cast<hipStream_t>(stream), prm.top_s, prm.top_i, n);
+                       static_cast<hipStream_t>(stream), prm.top_s, prm.top_i, prm.top_g, n);
     const hipError_t e = hipGetLastError();
     return e == hipSuccess ? MINER_OK : (int)e;
   }
@@ -1708,8 +1804,33 @@ int rk_run(void* stream, int dtype, RkParams prm, void* workspace, size_t worksp
   }
   if (prm.E == 0) prm.excl = nullptr;
   if (!subset) { prm.ids = nullptr; prm.M = 0; }
-  if (prm.clus == nullptr) prm.cap = 0;
+  if (prm.clus == nullptr) prm.cap = prm.icap;       // (0 without either kind of cap)
   return rk_dispatch(stream, dtype, prm, kRank);
+}
+
+// the checks the list-merge entry points start with, and their one launch
+int merge_check(const float* a_scores, const int32_t* a_ids, int ka, const float* b_scores, const int32_t* b_ids, int kb,
+                int U, int topk, const uint32_t* news_ok, int N, float* out_scores, int32_t* out_ids) {
+  if (U < 0 || ka < 0 || kb < 0 || topk <= 0) return MINER_EINVAL;
+  if (ka > kMaxTopk || kb > kMaxTopk || topk > kMaxTopk) return MINER_ESHAPE;
+  if ((ka > 0 && (!a_scores || !a_ids)) || (kb > 0 && (!b_scores || !b_ids)) || !out_scores || !out_ids) return MINER_EINVAL;
+  if (news_ok && N <= 0) return MINER_EINVAL;
+  if (!aligned4(a_scores) || !aligned4(a_ids) || !aligned4(b_scores) || !aligned4(b_ids) || !aligned4(news_ok) ||
+      !aligned4(out_scores) || !aligned4(out_ids))
+    return MINER_EALIGN;
+  return MINER_OK;
+}
+using MergeKernel = void (*)(const float*, const int32_t*, int, const float*, const int32_t*, int, int, int, const uint32_t*,
+                             int, float*, int32_t*, const int32_t*, int, int, const int32_t*, const int32_t*, int32_t*);
+int merge_launch(MergeKernel kern, void* stream, const float* a_scores, const int32_t* a_ids, int ka, const float* b_scores,
+                 const int32_t* b_ids, int kb, int U, int topk, const uint32_t* news_ok, int N, float* out_scores,
+                 int32_t* out_ids, const int32_t* clus, int n_clus, int cap, const int32_t* a_groups,
+                 const int32_t* b_groups, int32_t* out_groups) {
+  hipLaunchKernelGGL(kern, dim3((U + kMergeUsers - 1) / kMergeUsers), dim3(64 * kMergeUsers), 0,
+                     static_cast<hipStream_t>(stream), a_scores, a_ids, ka, b_scores, b_ids, kb, U, topk, news_ok, N,
+                     out_scores, out_ids, clus, n_clus, cap, a_groups, b_groups, out_groups);
+  const hipError_t e = hipGetLastError();
+  return e == hipSuccess ? MINER_OK : (int)e;
 }
 
 }  // namespace
@@ -1725,17 +1846,28 @@ int miner_score_pairs(void* stream, int dtype, int score_type, const void* user_
 int miner_score_pairs_biased(void* stream, int dtype, int score_type, const void* user_mui, const void* user_proj,
                              const void* news, int U, int N, int d, int K, const int32_t* cand_ids, int C, float* scores,
                              const float* news_bias, int G, const int32_t* user_group) {
+  return miner_score_pairs_interest(stream, dtype, score_type, user_mui, user_proj, news, U, N, d, K, cand_ids, C, scores,
+                                    news_bias, G, user_group, nullptr);
+}
+
+int miner_score_pairs_interest(void* stream, int dtype, int score_type, const void* user_mui, const void* user_proj,
+                               const void* news, int U, int N, int d, int K, const int32_t* cand_ids, int C, float* scores,
+                               const float* news_bias, int G, const int32_t* user_group, int32_t* interests) {
   RkParams prm{};
   prm.mui = user_mui; prm.proj = user_proj; prm.news = news; prm.top_s = scores;
   prm.U = U; prm.N = N; prm.d = d; prm.K = K; prm.score_type = score_type;
   prm.ids = cand_ids; prm.M = C;
   prm.bias = news_bias; prm.grp = user_group; prm.G = G;
+  prm.top_g = interests;
   const int ck = rk_check_common(dtype, prm, false);
   if (ck != MINER_OK) return ck;
   if (C < 0 || (C > 0 && (!cand_ids || !scores))) return MINER_EINVAL;
   if (!aligned4(cand_ids) || !aligned4(scores)) return MINER_EALIGN;
   const int bk = bias_check(prm);
   if (bk != MINER_OK) return bk;
+  // the interests: a score type that has a dominant interest, then the alignment
+  if (interests != nullptr && score_type == MINER_SCORE_MEAN) return MINER_EINVAL;
+  if (!aligned4(interests)) return MINER_EALIGN;
   if (U == 0 || C == 0) return MINER_OK;
   return rk_dispatch(stream, dtype, prm, kPair);
 }
@@ -1885,6 +2017,17 @@ int miner_rank_topk_after(void* stream, int dtype, int score_type, const void* u
                           void* workspace, size_t workspace_bytes, const float* news_bias, int G,
                           const int32_t* user_group, const int32_t* news_cluster, int cap, const float* after_scores,
                           const int32_t* after_ids) {
+  return miner_rank_topk_interest(stream, dtype, score_type, user_mui, user_proj, news, U, N, d, K, topk, exclude_ids, E,
+                                  news_ok, news_ids, M, top_scores, top_ids, workspace, workspace_bytes, news_bias, G,
+                                  user_group, news_cluster, cap, after_scores, after_ids, 0, nullptr);
+}
+
+int miner_rank_topk_interest(void* stream, int dtype, int score_type, const void* user_mui, const void* user_proj,
+                             const void* news, int U, int N, int d, int K, int topk, const int32_t* exclude_ids, int E,
+                             const uint32_t* news_ok, const int32_t* news_ids, int M, float* top_scores, int32_t* top_ids,
+                             void* workspace, size_t workspace_bytes, const float* news_bias, int G,
+                             const int32_t* user_group, const int32_t* news_cluster, int cap, const float* after_scores,
+                             const int32_t* after_ids, int interest_cap, int32_t* top_interest) {
   RkParams prm{};
   prm.mui = user_mui; prm.proj = user_proj; prm.news = news; prm.top_s = top_scores; prm.top_i = top_ids;
   prm.U = U; prm.N = N; prm.d = d; prm.K = K; prm.topk = topk; prm.score_type = score_type;
@@ -1893,6 +2036,7 @@ int miner_rank_topk_after(void* stream, int dtype, int score_type, const void* u
   prm.bias = news_bias; prm.grp = user_group; prm.G = G;
   prm.clus = news_cluster; prm.cap = cap;
   prm.aft_s = after_scores; prm.aft_i = after_ids;
+  prm.icap = interest_cap; prm.top_g = top_interest;
   return rk_run(stream, dtype, prm, workspace, workspace_bytes);
 }
 
@@ -1906,26 +2050,31 @@ int miner_topk_merge(void* stream, const float* a_scores, const int32_t* a_ids, 
 int miner_topk_merge_capped(void* stream, const float* a_scores, const int32_t* a_ids, int ka, const float* b_scores,
                             const int32_t* b_ids, int kb, int U, int topk, const uint32_t* news_ok, int N,
                             float* out_scores, int32_t* out_ids, const int32_t* news_cluster, int n_cluster, int cap) {
-  if (U < 0 || ka < 0 || kb < 0 || topk <= 0) return MINER_EINVAL;
-  if (ka > kMaxTopk || kb > kMaxTopk || topk > kMaxTopk) return MINER_ESHAPE;
-  if ((ka > 0 && (!a_scores || !a_ids)) || (kb > 0 && (!b_scores || !b_ids)) || !out_scores || !out_ids) return MINER_EINVAL;
-  if (news_ok && N <= 0) return MINER_EINVAL;
-  if (!aligned4(a_scores) || !aligned4(a_ids) || !aligned4(b_scores) || !aligned4(b_ids) || !aligned4(news_ok) ||
-      !aligned4(out_scores) || !aligned4(out_ids))
-    return MINER_EALIGN;
+  const int ck = merge_check(a_scores, a_ids, ka, b_scores, b_ids, kb, U, topk, news_ok, N, out_scores, out_ids);
+  if (ck != MINER_OK) return ck;
   const int cc = cap_check(news_cluster, cap);
   if (cc != MINER_OK) return cc;
   if (news_cluster != nullptr && n_cluster <= 0) return MINER_EINVAL;
   if (!aligned4(news_cluster)) return MINER_EALIGN;
   if (U == 0) return MINER_OK;
   // (the capped instantiation only with a table: the plain merge launches the kernel it did)
-  void (*kern)(const float*, const int32_t*, int, const float*, const int32_t*, int, int, int, const uint32_t*, int, float*,
-               int32_t*, const int32_t*, int, int) = news_cluster != nullptr ? topk_merge<true> : topk_merge<false>;
-  hipLaunchKernelGGL(kern, dim3((U + kMergeUsers - 1) / kMergeUsers), dim3(64 * kMergeUsers), 0,
-                     static_cast<hipStream_t>(stream), a_scores, a_ids, ka, b_scores, b_ids, kb, U, topk, news_ok, N,
-                     out_scores, out_ids, news_cluster, n_cluster, cap);
-  const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? MINER_OK : (int)e;
+  return merge_launch(news_cluster != nullptr ? topk_merge<1> : topk_merge<0>, stream, a_scores, a_ids, ka, b_scores, b_ids,
+                      kb, U, topk, news_ok, N, out_scores, out_ids, news_cluster, n_cluster, cap, nullptr, nullptr, nullptr);
+}
+
+int miner_topk_merge_grouped(void* stream, const float* a_scores, const int32_t* a_ids, int ka, const float* b_scores,
+                             const int32_t* b_ids, int kb, int U, int topk, const uint32_t* news_ok, int N,
+                             float* out_scores, int32_t* out_ids, const int32_t* a_groups, const int32_t* b_groups,
+                             int32_t* out_groups, int cap) {
+  const int ck = merge_check(a_scores, a_ids, ka, b_scores, b_ids, kb, U, topk, news_ok, N, out_scores, out_ids);
+  if (ck != MINER_OK) return ck;
+  if (cap < 0) return MINER_EINVAL;
+  if (cap > kMaxTopk) return MINER_ESHAPE;
+  if ((ka > 0 && !a_groups) || (kb > 0 && !b_groups) || !out_groups) return MINER_EINVAL;
+  if (!aligned4(a_groups) || !aligned4(b_groups) || !aligned4(out_groups)) return MINER_EALIGN;
+  if (U == 0) return MINER_OK;
+  return merge_launch(topk_merge<2>, stream, a_scores, a_ids, ka, b_scores, b_ids, kb, U, topk, news_ok, N, out_scores,
+                      out_ids, nullptr, 0, cap, a_groups, b_groups, out_groups);
 }
 
 }  // extern "C"
