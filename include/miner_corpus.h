@@ -33,6 +33,10 @@
  *                             which of the user's K interests a news matched (the arg-max of the
  *                             score's own reduction over K), and lists with at most `interest_cap`
  *                             news of one dominant interest.
+ *   miner_rank_topk_resume(...), miner_walk_advance(...)
+ *                             a capped list continued on a later page: the cursor together with a
+ *                             per-user table of how many entries of each group were already served,
+ *                             and that state advanced by a served page on the device.
  *
  * Conventions are those of miner_score.h. dtype: MINER_DTYPE_F32 (exact fp32, parity mode),
  * MINER_DTYPE_BF16 or MINER_DTYPE_F16 (16-bit operands, fp32 accumulation and softmax).
@@ -314,8 +318,9 @@ int miner_topk_merge_capped(void* stream, const float* a_scores, const int32_t* 
  *   a NaN score       lists nothing.
  * The cursor need not be a listed news: an id that is excluded, ineligible, outside news_ids,
  * negative or past N is a position in the order like any other. Split and unsplit forms agree bit
- * for bit (every slice applies the cursor). There is no cursor under caps: a capped walk also needs
- * the per-cluster counts of the earlier pages, which a (score, id) pair does not carry.
+ * for bit (every slice applies the cursor). A cursor alone does not continue a capped list: a capped
+ * walk also needs the per-cluster counts of the earlier pages, which a (score, id) pair does not
+ * carry — this entry refuses the pair, and miner_rank_topk_resume (below) takes those counts.
  *
  * miner_rank_topk_after: miner_rank_topk_capped's arguments, then the two above. With both NULL it
  * returns exactly what miner_rank_topk_capped returns on the other arguments (it launches the same
@@ -368,7 +373,7 @@ int miner_rank_topk_after(void* stream, int dtype, int score_type, const void* u
  * table g_u[n] = interest(u, n) (news_cluster cannot express it for more than one user: its cluster
  * belongs to the news, the dominant interest to the pair). As the capped form: the UNSPLIT kernel
  * whatever the workspace (accepted, never written), over the table or the id list, with or without
- * a prior; no cursor, and never together with news_cluster. After miner_rank_topk_after's own
+ * a prior; no bare cursor (miner_rank_topk_resume continues it), and never together with news_cluster. After miner_rank_topk_after's own
  * checks, in their order and with their codes: interest_cap < 0: MINER_EINVAL;
  * interest_cap > MINER_CORPUS_MAX_TOPK: MINER_ESHAPE; a cap with a non-NULL news_cluster or with a
  * cursor: MINER_EINVAL; a cap with MINER_SCORE_MEAN: MINER_EINVAL; top_interest without a cap:
@@ -405,6 +410,79 @@ int miner_topk_merge_grouped(void* stream, const float* a_scores, const int32_t*
                              const float* b_scores, const int32_t* b_ids, int kb, int U, int topk,
                              const uint32_t* news_ok, int N, float* out_scores, int32_t* out_ids,
                              const int32_t* a_groups, const int32_t* b_groups, int32_t* out_groups, int cap);
+
+#define MINER_CORPUS_MAX_WALK_GROUPS 1024
+
+/*
+ * The resumed capped walk: a cursor under caps. A capped list (news_cluster / cap, or interest_cap)
+ * continued on a later page needs, beside the (score, id) cursor, how many entries of each group the
+ * earlier pages served. For user u the WALK STATE is
+ *   a cursor (after_scores[u], after_ids[u]), and
+ *   a table of n_used[u] pairs (used_groups[u][i], used_counts[u][i]), i < n_used[u], the groups
+ *   STRICTLY ASCENDING and all >= 0 — a group is a cluster id under news_cluster, an interest in [0, K)
+ *   under interest_cap. used(g) is the count of g's pair, 0 for a group not in the table; a negative
+ *   count reads as 0.
+ *   used_groups / used_counts [U, Q] int32 row-major, n_used [U] int32, device pointers, 4-byte
+ *   aligned, 0 <= Q <= MINER_CORPUS_MAX_WALK_GROUPS. Only the first n_used[u] pairs of a row are read.
+ *   Sortedness is a precondition, as the distinctness of news_ids is: over an unsorted table the
+ *   lookup may miss a pair (its group then counts from 0). n_used[u] outside [0, Q] is the caller's
+ *   error; the device clamps it into [0, Q], so no address leaves the table. The tables are only read.
+ * The resumed list is the walk of u's complete ranking — under exclude_ids, news_ok, news_ids and
+ * news_bias, score descending, then lower id — over the entries STRICTLY AFTER the cursor
+ * (miner_rank_topk_after's rule, on the ranked value and the table id): an entry is kept iff its
+ * group is negative or used(g) + (entries of g kept earlier in this call) < cap; the walk stops after
+ * topk kept entries, then (-inf, -1). Listed scores are the uncapped call's, bit for bit; an excluded
+ * or ineligible news spends no cap; a NaN score is never listed and a NaN cursor lists nothing. So
+ * the pages chained through the state — the next state is the page's cursor (page_cursor's rule)
+ * plus the old counts plus the groups of the page's kept entries: miner_walk_advance — concatenate to
+ * the capped walk of any depth, also when cap or topk change between pages (both are read per call).
+ * An empty table at (+inf, -1) gives miner_rank_topk_interest's capped list, bit for bit.
+ * As the capped form: the UNSPLIT kernel whatever the workspace, over the table or the id list, with
+ * or without a prior; one kind of cap per call; not for MINER_SCORE_MEAN with interests.
+ *
+ * miner_rank_topk_resume: miner_rank_topk_interest's arguments, then the three tables and Q. With
+ * all three NULL it returns exactly what miner_rank_topk_interest returns (it launches the same
+ * kernel; a cursor under caps is still MINER_EINVAL; Q is not read). With a table: that call's own
+ * checks first, in their order and with their codes, except its refusal of a cursor under a cap; then
+ * no cursor: MINER_EINVAL; neither kind of cap: MINER_EINVAL; Q < 0 or a NULL among the three:
+ * MINER_EINVAL; Q > MINER_CORPUS_MAX_WALK_GROUPS: MINER_ESHAPE; a misaligned table pointer:
+ * MINER_EALIGN (all before any launch, and before the U == 0 return).
+ *
+ * miner_walk_advance: the state after a served page, on the device (one small launch; a feed loop or
+ * a deep list needs no host synchronisation).
+ *   page_scores / page_ids [U, k], 1 <= k <= MINER_CORPUS_MAX_TOPK: the page as the ranker returned it.
+ *   page_groups [U, k] int32 or NULL: the group of each entry (the interests listed with it); NULL:
+ *               the group is news_cluster[id] (n_cluster entries; an id at or past n_cluster has no
+ *               group and no word is read for it). An entry with id < 0 (the tail) or a negative group
+ *               adds nothing.
+ *   in_groups / in_counts [U, Q_in], in_n_used [U]: the state's table (as above; n clamped).
+ *   out_after_scores / out_after_ids [U]: the row's last entry if the row is full, else
+ *               (-inf, 2^31 - 1) — "after everything": the ranking ended.
+ *   out_groups / out_counts [U, Q], out_n_used [U]: the union, strictly ascending, counts summed
+ *               (a negative in count as 0). Distinct from the in buffers.
+ *   overflow    [U] uint8 out: 1 if user u needs more than Q distinct groups — then its cursor
+ *               becomes (-inf, 2^31 - 1), so its ranking ends rather than ever breaking a cap (the Q
+ *               lowest groups are written); else 0.
+ * U < 0, k <= 0, Q < 0 or Q_in < 0: MINER_EINVAL; k > MINER_CORPUS_MAX_TOPK, Q or Q_in >
+ * MINER_CORPUS_MAX_WALK_GROUPS: MINER_ESHAPE; a NULL page, in_n_used or output pointer, NULL in
+ * tables with Q_in > 0, NULL out tables with Q > 0: MINER_EINVAL; neither page_groups nor a
+ * news_cluster with n_cluster > 0: MINER_EINVAL; a misaligned pointer: MINER_EALIGN (all before any
+ * launch, and before the U == 0 return).
+ */
+int miner_rank_topk_resume(void* stream, int dtype, int score_type, const void* user_mui,
+                           const void* user_proj, const void* news, int U, int N, int d, int K, int topk,
+                           const int32_t* exclude_ids, int E, const uint32_t* news_ok,
+                           const int32_t* news_ids, int M, float* top_scores, int32_t* top_ids,
+                           void* workspace, size_t workspace_bytes, const float* news_bias, int G,
+                           const int32_t* user_group, const int32_t* news_cluster, int cap,
+                           const float* after_scores, const int32_t* after_ids, int interest_cap,
+                           int32_t* top_interest, const int32_t* used_groups, const int32_t* used_counts,
+                           const int32_t* n_used, int Q);
+int miner_walk_advance(void* stream, const float* page_scores, const int32_t* page_ids,
+                       const int32_t* page_groups, const int32_t* news_cluster, int n_cluster,
+                       const int32_t* in_groups, const int32_t* in_counts, const int32_t* in_n_used, int Q_in,
+                       float* out_after_scores, int32_t* out_after_ids, int32_t* out_groups,
+                       int32_t* out_counts, int32_t* out_n_used, uint8_t* overflow, int U, int k, int Q);
 
 #ifdef __cplusplus
 }

@@ -67,6 +67,9 @@ SIGNATURES = {
     "miner_rank_topk_interest": (_I, [_P, _I, _I, _P, _P, _P, _I, _I, _I, _I, _I, _P, _I, _P, _P, _I, _P, _P, _P,
                                       ctypes.c_size_t, _P, _I, _P, _P, _I, _P, _P, _I, _P]),
     "miner_topk_merge_grouped": (_I, [_P, _P, _P, _I, _P, _P, _I, _I, _I, _P, _I, _P, _P, _P, _P, _P, _I]),
+    "miner_rank_topk_resume": (_I, [_P, _I, _I, _P, _P, _P, _I, _I, _I, _I, _I, _P, _I, _P, _P, _I, _P, _P, _P,
+                                    ctypes.c_size_t, _P, _I, _P, _P, _I, _P, _P, _I, _P, _P, _P, _P, _I]),
+    "miner_walk_advance": (_I, [_P, _P, _P, _P, _P, _I, _P, _P, _P, _I, _P, _P, _P, _P, _P, _P, _I, _I, _I]),
     # include/miner_news.h
     "miner_news_precompute": (_I, [_P, _I, _P, _I, _P, _I, _I, _I, _P, _P]),
     "miner_score_news": (_I, [_P, _I, _I, _P, _P, _P, _I, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P]),

@@ -124,6 +124,7 @@ ASAN_DRIVER_BIAS = os.path.join(ROOT, "tests", "native", "abi_errors_bias.cpp")
 ASAN_DRIVER_CAP = os.path.join(ROOT, "tests", "native", "abi_errors_cap.cpp")
 ASAN_DRIVER_AFTER = os.path.join(ROOT, "tests", "native", "abi_errors_after.cpp")
 ASAN_DRIVER_INTEREST = os.path.join(ROOT, "tests", "native", "abi_errors_interest.cpp")
+ASAN_DRIVER_RESUME = os.path.join(ROOT, "tests", "native", "abi_errors_resume.cpp")
 
 
 def build_asan_driver(force: bool = False, verbose: bool = False, driver: str = ASAN_DRIVER) -> str:
@@ -207,6 +208,12 @@ def build_asan_driver_interest(force: bool = False, verbose: bool = False) -> st
     return build_asan_driver(force=force, verbose=verbose, driver=ASAN_DRIVER_INTEREST)
 
 
+def build_asan_driver_resume(force: bool = False, verbose: bool = False) -> str:
+    """build/asan/abi_errors_resume: the error paths of miner_rank_topk_resume and miner_walk_advance
+    (tests/native/abi_errors_resume.cpp; run by tests/test_corpus_resume_host.py)."""
+    return build_asan_driver(force=force, verbose=verbose, driver=ASAN_DRIVER_RESUME)
+
+
 if __name__ == "__main__":
     if "--asan" in sys.argv:
         print(build_asan_driver(force="--force" in sys.argv, verbose=True))
@@ -216,5 +223,6 @@ if __name__ == "__main__":
         print(build_asan_driver_cap(verbose=True))
         print(build_asan_driver_after(verbose=True))
         print(build_asan_driver_interest(verbose=True))
+        print(build_asan_driver_resume(verbose=True))
     else:
         print(build_library(force="--force" in sys.argv, verbose=True, debug="--debug" in sys.argv))

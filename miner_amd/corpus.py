@@ -29,6 +29,10 @@ d=768, fp16), backed by libminer_hip.so (include/miner_corpus.h).
                                                            # dominant interest per list; triples through merge_topk /
                                                            # update_topk(interest_cap=) (unsplit kernel only, no cursor;
                                                            # not rank_of / evaluate_corpus / rescore_topk)
+    state = start_walk(U, device)                          # the cursor under caps: a WalkState carries the cursor and
+    page = rank_topk(..., cluster_cap=1, resume=state)     # the per-group counts of the pages served so far;
+    state = advance_walk(state, page, news_cluster=story)  # advanced on the device; also rank_corpus(resume=) and
+    deep = rank_topk_deep_capped(..., 1000, cluster_cap=1) # capped lists of any depth (not merge_topk / update_topk / cap_topk)
 
 The click score of (user, news) is the reference's (src/model/model.py:127-134, 213-214) with the
 impression's candidate set replaced by the whole news table; ties rank the lower news id first.
@@ -360,11 +364,151 @@ def page_cursor(lists):
             torch.where(full, last_i, _INT32_MAX).to(torch.int32).contiguous())
 
 
+MAX_WALK_GROUPS = 1024
+
+
+@dataclasses.dataclass
+class WalkState:
+    """The state of a capped walk between two pages (include/miner_corpus.h, miner_rank_topk_resume):
+    per user the keyset cursor — scores fp32 [U], ids int32 [U] — and the table of the groups served so
+    far: groups / counts int32 [U, Q] (the first n_used[u] pairs of row u, groups strictly ascending
+    and >= 0: cluster ids under news_cluster, interests under interest_cap), n_used int32 [U], and
+    overflow uint8 [U] (1: the user needed more than Q distinct groups and its walk was ended — its
+    cursor is "after everything" — rather than a cap ever broken). start_walk makes the first,
+    advance_walk the next; a hand-made one must keep the table sorted."""
+    scores: Tensor
+    ids: Tensor
+    groups: Tensor
+    counts: Tensor
+    n_used: Tensor
+    overflow: Tensor
+
+    @property
+    def cursor(self):
+        return self.scores, self.ids
+
+    @property
+    def capacity(self) -> int:
+        return self.groups.shape[1]
+
+    def users(self, u0: int, u1: int) -> "WalkState":
+        return WalkState(self.scores[u0:u1], self.ids[u0:u1], self.groups[u0:u1], self.counts[u0:u1], self.n_used[u0:u1],
+                         self.overflow[u0:u1])
+
+
+def _walk_state(state, U: Optional[int], on_device: bool = True) -> WalkState:
+    """resume= / advance_walk's state -> a checked WalkState with contiguous fields. Types, dtypes and
+    shapes are checked before anything touches the device (``on_device`` False: the caller checks
+    the device itself, after its other arguments)."""
+    if not isinstance(state, WalkState):
+        raise ValueError("resume must be a WalkState (start_walk, advance_walk)")
+    fields = (state.scores, state.ids, state.groups, state.counts, state.n_used, state.overflow)
+    if not all(isinstance(t, Tensor) for t in fields):
+        raise ValueError("WalkState: every field is a tensor")
+    n = state.scores.shape[0] if state.scores.dim() == 1 else -1
+    if U is not None and n != U:
+        raise ValueError(f"the walk state was made for {n} users, not {U}")
+    if state.scores.dtype != torch.float32 or state.scores.dim() != 1 or state.ids.dtype != torch.int32 \
+            or tuple(state.ids.shape) != (n,):
+        raise ValueError(f"WalkState: the cursor is scores float32 [{n}] and ids int32 [{n}]")
+    if state.groups.dtype != torch.int32 or state.counts.dtype != torch.int32 or state.groups.dim() != 2 \
+            or state.groups.shape[0] != n or state.counts.shape != state.groups.shape \
+            or state.groups.shape[1] > MAX_WALK_GROUPS:
+        raise ValueError(f"WalkState: groups and counts are int32 [{n}, Q] of one shape, Q <= {MAX_WALK_GROUPS}")
+    if state.n_used.dtype != torch.int32 or tuple(state.n_used.shape) != (n,) or state.overflow.dtype != torch.uint8 \
+            or tuple(state.overflow.shape) != (n,):
+        raise ValueError(f"WalkState: n_used is int32 [{n}] and overflow uint8 [{n}]")
+    if on_device:
+        _require_device(*fields)
+    return WalkState(*(t.contiguous() for t in fields))
+
+
+def _capacity(capacity) -> int:
+    if isinstance(capacity, bool) or not isinstance(capacity, int) or not 0 <= capacity <= MAX_WALK_GROUPS:
+        raise ValueError(f"capacity must be an int in [0, {MAX_WALK_GROUPS}]")
+    return capacity
+
+
+def start_walk(U: int, device, capacity: int = MAX_WALK_GROUPS) -> WalkState:
+    """The state before everything: the cursor (+inf, -1) and an empty table with room for
+    ``capacity`` distinct groups per user (at most 1,024). rank_topk(..., resume=start_walk(...)) is
+    the first page — the capped list of the call without ``resume``, bit for bit."""
+    Q = _capacity(capacity)
+    s, i = start_cursor(U, device)
+    return WalkState(s, i, torch.zeros(U, Q, dtype=torch.int32, device=device),
+                     torch.zeros(U, Q, dtype=torch.int32, device=device), torch.zeros(U, dtype=torch.int32, device=device),
+                     torch.zeros(U, dtype=torch.uint8, device=device))
+
+
+def advance_walk(state: WalkState, page, *, news_cluster=None) -> WalkState:
+    """The state after ``page`` was served from ``state`` (miner_walk_advance: one small launch, no
+    host synchronisation): the page's page_cursor, and the state's table plus the groups of the page's
+    entries — a (scores, ids) pair under ``news_cluster`` (the integer table, or rank_topk's checked
+    caps; an id at or past its length has no group), or a (scores, ids, interests) triple without it,
+    as rank_topk(interest_cap=, return_interest=True) returns. Tail entries and entries in no group
+    add nothing. The new state has the old one's capacity; a user that would need more distinct
+    groups gets overflow 1 and the cursor "after everything" (its next page is empty), and an
+    overflow stays set in the states that follow. The arguments are checked before anything touches
+    the device; the outputs are new tensors."""
+    triple = _is_triple(page)
+    if triple == (news_cluster is not None):
+        raise ValueError("advance_walk: a (scores, ids) page with news_cluster, or a (scores, ids, interests) page without")
+    st = _walk_state(state, None, on_device=False)
+    U, Q = st.groups.shape
+    if not triple:
+        try:
+            ps, pi = page
+        except (TypeError, ValueError):
+            raise ValueError("page must be a (scores, ids) pair or a (scores, ids, interests) triple")
+    else:
+        ps, pi = page[0], page[1]
+    if not isinstance(ps, Tensor) or not isinstance(pi, Tensor) or ps.dim() != 2 or ps.shape != pi.shape \
+            or not ps.is_floating_point() or pi.is_floating_point() or pi.dtype == torch.bool or ps.shape[0] != U \
+            or not 1 <= ps.shape[1] <= MAX_TOPK:
+        raise ValueError(f"page: scores [{U},k] and integer ids [{U},k] of one shape, 1 <= k <= {MAX_TOPK}")
+    pg = clus = None
+    if triple:
+        pg = page[2]
+        if not isinstance(pg, Tensor) or pg.shape != ps.shape or pg.is_floating_point() or pg.is_complex() \
+                or pg.dtype == torch.bool:
+            raise ValueError("page: integer interests of the page's shape [U,k]")
+    else:
+        clus = _caps(news_cluster, None if isinstance(news_cluster, _Caps) else 1, None).cluster
+    _require_device(ps, pi, pg, st.scores, st.ids, st.groups, st.counts, st.n_used, st.overflow)
+    ps, pi, pg = _contig(ps, torch.float32), _contig(pi, torch.int32), _contig(pg, torch.int32)
+    dev = ps.device
+    k = ps.shape[1]
+    out = WalkState(torch.empty(U, dtype=torch.float32, device=dev), torch.empty(U, dtype=torch.int32, device=dev),
+                    torch.zeros(U, Q, dtype=torch.int32, device=dev), torch.zeros(U, Q, dtype=torch.int32, device=dev),
+                    torch.empty(U, dtype=torch.int32, device=dev), torch.empty(U, dtype=torch.uint8, device=dev))
+    with torch.cuda.device(dev):
+        rc = _lib.lib().miner_walk_advance(_stream(dev), _ptr(ps), _ptr(pi), _ptr(pg), _ptr(clus),
+                                           0 if clus is None else clus.shape[0], _ptr(st.groups) if Q else None,
+                                           _ptr(st.counts) if Q else None, _ptr(st.n_used), Q, _ptr(out.scores), _ptr(out.ids),
+                                           _ptr(out.groups) if Q else None, _ptr(out.counts) if Q else None, _ptr(out.n_used),
+                                           _ptr(out.overflow), U, k, Q)
+    _lib.check(rc, "miner_walk_advance")
+    out.overflow |= st.overflow
+    return out
+
+
+def _resume_args(resume, after, capped: bool, U: int) -> Optional[WalkState]:
+    """resume= of the ranking entries -> a checked WalkState, or None without one. A resumed walk
+    continues a capped list: it needs a cap, and it carries its own cursor."""
+    if resume is None:
+        return None
+    if after is not None:
+        raise ValueError("resume= carries its own cursor: it cannot be combined with after=")
+    if not capped:
+        raise ValueError("resume= continues a capped list: it needs news_cluster / cluster_cap or interest_cap")
+    return _walk_state(resume, U)
+
+
 def rank_topk(user_mui: Tensor, user_proj: Optional[Tensor], news: Tensor, topk: int, *,
               score_type: str = "weighted", exclude_ids: Optional[Tensor] = None,
               eligible: Optional[Tensor] = None, news_ids=None, news_bias=None,
               user_group: Optional[Tensor] = None, news_cluster=None, cluster_cap: Optional[int] = None,
-              after=None, interest_cap: Optional[int] = None, return_interest: bool = False):
+              after=None, interest_cap: Optional[int] = None, return_interest: bool = False, resume=None):
     """Top-k news per user by the click score, best first: (scores [U,topk] fp32, ids [U,topk]
     int32); entries past the table size are (-inf, -1).
 
@@ -409,9 +553,19 @@ def rank_topk(user_mui: Tensor, user_proj: Optional[Tensor], news: Tensor, topk:
     page_cursor are disjoint and concatenate to the complete ranking. (+inf, -1) is before
     everything, (-inf, 2^31 - 1) after everything, a NaN score lists nothing, and the cursor need not
     be a listed, eligible or existing news: it is a position in the order. Each page streams the
-    table once (the price: profiles/rk_after_ab.txt). There is no cursor under caps (a capped walk
-    also needs the earlier pages' per-cluster counts): ``after`` with news_cluster / cluster_cap
-    raises ValueError. Without ``after`` the call is today's.
+    table once (the price: profiles/rk_after_ab.txt). A cursor alone does not continue a capped list
+    (a capped walk also needs the earlier pages' per-cluster counts): ``after`` with news_cluster /
+    cluster_cap raises ValueError — ``resume`` is the way. Without ``after`` the call is today's.
+
+    resume: a WalkState (start_walk, advance_walk) — the cursor under caps. With news_cluster /
+    cluster_cap or interest_cap (one of them; without a cap, or together with ``after``: ValueError) the
+    list is the capped walk continued strictly after the state's cursor, in which a group g already
+    has state.counts' used(g) entries: an entry is kept iff it is in no group or used(g) + (entries of
+    g kept earlier in this call) < cap. Scores are the uncapped call's, bit for bit, and the pages
+    chained with advance_walk concatenate to the capped walk of any depth — also when the cap or topk
+    change between pages. resume=start_walk(...) is the call without it, bit for bit.
+    ``return_interest`` works as under interest_cap. The unsplit kernel, as every capped call; the
+    price: profiles/rk_resume_ab.txt. Without ``resume`` the call is today's.
 
     return_interest: the call returns (scores, ids, interests): interests int32 [U,topk], the
     dominant interest of each listed pair — the lowest k in [0, K) whose value equals the maximum
@@ -434,9 +588,10 @@ def rank_topk(user_mui: Tensor, user_proj: Optional[Tensor], news: Tensor, topk:
     capped step: profiles/rk_interest_ab.txt. With neither the call is today's."""
     icap = _interest_args(interest_cap, return_interest, score_type, news_cluster, cluster_cap, after)
     _no_cursor_under_caps(after, news_cluster, cluster_cap)
+    walk = _resume_args(resume, after, news_cluster is not None or cluster_cap is not None or icap > 0, user_mui.shape[0])
     pri = _prior(news_bias, user_group, user_mui.shape[0], news.shape[0])
     caps = _caps(news_cluster, cluster_cap, news.shape[0])
-    cur = _cursor(after, user_mui.shape[0])
+    cur = _cursor(after, user_mui.shape[0]) if walk is None else _Cursor(walk.scores, walk.ids)
     st, dt, mui, proj, tab = _rank_operands(user_mui, user_proj, news, score_type)
     U, K, d = mui.shape
     N = tab.shape[0]
@@ -474,12 +629,19 @@ def rank_topk(user_mui: Tensor, user_proj: Optional[Tensor], news: Tensor, topk:
     top_g = torch.empty(U, topk, dtype=torch.int32, device=dev) if icap and return_interest else None
     with torch.cuda.device(dev):
         # the widest entry; what the call does not use is NULL and launches the narrower entry's kernel
-        rc = lib.miner_rank_topk_interest(_stream(dev), dt, st, _ptr(mui), _ptr(proj), _ptr(tab), U, N, d, K, topk,
-                                          _ptr(excl), E, _ptr(ok), _ptr(sub.ids) if M > 0 else None, M, _ptr(top_s),
-                                          _ptr(top_i), _ptr(ws), nws, *_prior_args(pri),
-                                          None if caps is None else _ptr(caps.cluster), 0 if caps is None else caps.cap,
-                                          None if cur is None else _ptr(cur.scores), None if cur is None else _ptr(cur.ids),
-                                          icap, _ptr(top_g))
+        args = (_stream(dev), dt, st, _ptr(mui), _ptr(proj), _ptr(tab), U, N, d, K, topk,
+                _ptr(excl), E, _ptr(ok), _ptr(sub.ids) if M > 0 else None, M, _ptr(top_s),
+                _ptr(top_i), _ptr(ws), nws, *_prior_args(pri),
+                None if caps is None else _ptr(caps.cluster), 0 if caps is None else caps.cap,
+                None if cur is None else _ptr(cur.scores), None if cur is None else _ptr(cur.ids),
+                icap, _ptr(top_g))
+        if walk is None:
+            rc = lib.miner_rank_topk_interest(*args)
+        else:
+            # (an empty [U, 0] table has no storage: any aligned non-NULL address stands for it, never read)
+            Q = walk.capacity
+            rc = lib.miner_rank_topk_resume(*args, _ptr(walk.groups) if Q else _ptr(walk.n_used),
+                                            _ptr(walk.counts) if Q else _ptr(walk.n_used), _ptr(walk.n_used), Q)
     _lib.check(rc, "miner_rank_topk")
     if not return_interest:
         return top_s, top_i
@@ -499,9 +661,9 @@ def rank_topk_deep(user_mui: Tensor, user_proj: Optional[Tensor], news: Tensor, 
     once, so the cost is pages x the rank_topk step (profiles/rk_after_ab.txt), not one pass: a deep
     list is paid for by its depth. The other arguments are rank_topk's; ``news_ids`` is canonicalised
     once, the bitmap packed once and the prior checked once. No host synchronisation beyond
-    rank_topk's own argument checks. Per-cluster caps are not offered (no cursor under caps):
-    ``news_cluster`` / ``cluster_cap`` are named only to say so, anything but None raises ValueError;
-    so is ``interest_cap``. ``return_interest`` (per page, as in rank_topk) adds interests [U,topk]
+    rank_topk's own argument checks. Caps are not offered here (a cursor alone does not continue a
+    capped list; rank_topk_deep_capped pages with walk states): ``news_cluster`` / ``cluster_cap`` are
+    named only to say so, anything but None raises ValueError; so is ``interest_cap``. ``return_interest`` (per page, as in rank_topk) adds interests [U,topk]
     int32 as a third result."""
     if news_cluster is not None or cluster_cap is not None:
         raise ValueError("rank_topk_deep pages with cursors, and there is no cursor under news_cluster / cluster_cap")
@@ -530,6 +692,62 @@ def rank_topk_deep(user_mui: Tensor, user_proj: Optional[Tensor], news: Tensor, 
         if k1 < topk:
             cur = _Cursor(*page_cursor(page[:2]))
     return (top_s, top_i, top_g) if return_interest else (top_s, top_i)
+
+
+def rank_topk_deep_capped(user_mui: Tensor, user_proj: Optional[Tensor], news: Tensor, topk: int, *, resume=None,
+                          return_state: bool = False, score_type: str = "weighted",
+                          exclude_ids: Optional[Tensor] = None, eligible: Optional[Tensor] = None, news_ids=None,
+                          news_bias=None, user_group: Optional[Tensor] = None, news_cluster=None, cluster_cap=None,
+                          interest_cap=None, return_interest: bool = False, capacity: int = MAX_WALK_GROUPS):
+    """The capped rank_topk for any topk >= 1 (news_cluster / cluster_cap, or interest_cap — one of
+    them): (scores [U,topk] fp32, ids [U,topk] int32), best first, with the (-inf, -1) tail —
+    ceil(topk / 256) resumed pages of rank_topk(resume=) chained with advance_walk on the device (the
+    first from ``resume``, or from start_walk(U, device, capacity) without it) and written side by
+    side. Every page streams the table once: the cost is pages x the resumed step
+    (profiles/rk_resume_ab.txt). The other arguments are rank_topk's; ``news_ids`` is canonicalised
+    once, the bitmap packed once, the prior and the caps checked once. No host synchronisation beyond
+    rank_topk's own argument checks. ``return_interest`` (under interest_cap) adds interests [U,topk]
+    int32 as a third result, ``return_state`` the WalkState after the last page as the last one: one
+    more rank_topk(resume=state) continues the walk.
+    A walk that starts from the empty state serves at most topk entries and so meets at most topk
+    distinct groups: topk <= capacity can never overflow. Beyond that (a deeper cluster-capped list,
+    or a ``resume`` state that already holds groups) a user that meets more than ``capacity`` distinct
+    groups gets state.overflow = 1 and its list ends there ((-inf, -1) from the next page on) rather
+    than a cap ever being broken; under interest_cap there are at most K <= 64 groups."""
+    if isinstance(topk, bool) or not isinstance(topk, int) or topk < 1:
+        raise ValueError("topk must be an int >= 1")
+    U, N = user_mui.shape[0], news.shape[0]
+    icap = _interest_args(interest_cap, return_interest, score_type, news_cluster, cluster_cap)
+    if (news_cluster is None and cluster_cap is None) == (icap == 0):
+        raise ValueError("rank_topk_deep_capped needs news_cluster / cluster_cap or interest_cap (one of them); "
+                         "rank_topk_deep is the uncapped deep list")
+    if return_interest and not icap:
+        raise ValueError("return_interest: the interests are listed under interest_cap")
+    Q = _capacity(capacity)
+    state = None if resume is None else _walk_state(resume, U)
+    pri = _prior(news_bias, user_group, U, N)
+    caps = _caps(news_cluster, cluster_cap, N)
+    _require_device(user_mui, user_proj, news, exclude_ids, eligible)
+    ok = None if eligible is None else _eligible_words(eligible, N)
+    sub = None if news_ids is None else _news_id_list(news_ids, N)
+    dev = user_mui.device
+    if state is None:
+        state = start_walk(U, dev, Q)
+    top_s = torch.empty(U, topk, dtype=torch.float32, device=dev)
+    top_i = torch.empty(U, topk, dtype=torch.int32, device=dev)
+    top_g = torch.empty(U, topk, dtype=torch.int32, device=dev) if return_interest else None
+    for k0 in range(0, topk, MAX_TOPK):
+        k1 = min(topk, k0 + MAX_TOPK)
+        page = rank_topk(user_mui, user_proj, news, k1 - k0, score_type=score_type, exclude_ids=exclude_ids,
+                         eligible=ok, news_ids=sub, news_bias=pri, news_cluster=caps, interest_cap=interest_cap,
+                         return_interest=icap > 0, resume=state)
+        top_s[:, k0:k1], top_i[:, k0:k1] = page[:2]
+        if return_interest:
+            top_g[:, k0:k1] = page[2]
+        if k1 < topk or return_state:
+            state = advance_walk(state, page, news_cluster=caps)
+    res = (top_s, top_i, top_g) if return_interest else (top_s, top_i)
+    return res + (state,) if return_state else res
 
 
 def _list_pair(lists, what: str):
@@ -578,7 +796,9 @@ def merge_topk(a, b, topk: Optional[int] = None, *, eligible: Optional[Tensor] =
     [1, 256]) runs the capped walk with the entry's own interest as its group — for disjoint A and B
     the interest-capped lists of one user merge to the interest-capped ranking of A ∪ B, bit for
     bit. A pair mixed with a triple, ``interest_cap`` with pairs, and ``interest_cap`` or triples
-    together with news_cluster / cluster_cap raise ValueError."""
+    together with news_cluster / cluster_cap raise ValueError. There is no ``resume=`` here: the merge
+    caps what its two lists hold, counting every group from 0 (a later page of a resumed walk is not
+    a capped list on its own, so pages are concatenated, not merged)."""
     triple = _is_triple(a)
     if triple != _is_triple(b):
         raise ValueError("merge_topk: both lists are (scores, ids) pairs or both (scores, ids, interests) triples")
@@ -666,7 +886,8 @@ def update_topk(lists, user_mui: Tensor, user_proj: Optional[Tensor], news: Tens
     ``eligible`` prunes an entry, or a re-ranked news comes back with a lower score, the
     same-interest news that entry once displaced is no longer in the list and does not return —
     within its caps, but possibly missing that news until the users are ranked again. (And the
-    interests in ``lists`` are those of the user vectors it was ranked with.)"""
+    interests in ``lists`` are those of the user vectors it was ranked with.) ``resume=`` is not
+    offered: ``lists`` is a first page (a capped list from the top), not a later page of a walk."""
     triple = _is_triple(lists)
     icap = _interest_args(interest_cap, triple, score_type, news_cluster, cluster_cap)
     if icap and not triple:
@@ -693,7 +914,7 @@ def cap_topk(lists, news_cluster, cluster_cap: int, topk: Optional[int] = None):
     a list is prefix-exact: capping an uncapped top-k gives the first entries of the true capped
     list, so the result IS rank_topk's capped list wherever it fills ``topk`` or the input list was
     not full (then the input held every admissible news); a row that comes back short from a full
-    input needs the capped ranker."""
+    input needs the capped ranker. Every group counts from 0: there is no ``resume=`` here."""
     caps = _caps(news_cluster, cluster_cap, None)
     s, i = _list_pair(lists, "lists")
     if s.shape[1] < 1:
@@ -971,7 +1192,7 @@ def rank_corpus(news: Tensor, his_ids: Tensor, his_mask: Tensor, packed: Encoder
                 out: Optional[tuple] = None, exclude_history: bool = False, exclude_ids: Optional[Tensor] = None,
                 eligible: Optional[Tensor] = None, news_ids=None, news_bias=None,
                 user_group: Optional[Tensor] = None, news_cluster=None, cluster_cap: Optional[int] = None,
-                after=None, interest_cap: Optional[int] = None, return_interest: bool = False):
+                after=None, interest_cap: Optional[int] = None, return_interest: bool = False, resume=None):
     """BASELINE config 5 on one GPU's share of the users: every user (his_ids [U,L] into the news
     table [N,d], his_mask [U,L]) encoded and ranked against the whole table, ``batch`` users per
     encode + rank pair so that the [batch,K,d] user vectors are all that is ever held (125,000 users
@@ -986,15 +1207,17 @@ def rank_corpus(news: Tensor, his_ids: Tensor, his_mask: Tensor, packed: Encoder
     (keyset cursors [U], checked once and sliced per batch; never together with the caps) too;
     ``interest_cap`` / ``return_interest`` (per-interest caps and the listed pairs' dominant interests,
     as in rank_topk) too: with ``return_interest`` the result, and ``out``, is a (scores, ids,
-    interests [U,topk] int32) triple."""
+    interests [U,topk] int32) triple. ``resume`` (a WalkState for all U users, checked once and sliced
+    per batch: the capped walk continued, as in rank_topk — it needs a cap and excludes ``after``) too."""
     if batch <= 0:
         raise ValueError("batch must be positive")
     U = his_ids.shape[0]
     dev = news.device
-    _interest_args(interest_cap, return_interest, score_type, news_cluster, cluster_cap, after)
+    icap = _interest_args(interest_cap, return_interest, score_type, news_cluster, cluster_cap, after)
     if out is not None and len(out) != (3 if return_interest else 2):
         raise ValueError("out must be (scores, ids), or (scores, ids, interests) with return_interest")
     _no_cursor_under_caps(after, news_cluster, cluster_cap)
+    walk = _resume_args(resume, after, news_cluster is not None or cluster_cap is not None or icap > 0, U)
     pri = _prior(news_bias, user_group, U, news.shape[0])
     caps = _caps(news_cluster, cluster_cap, news.shape[0])
     cur = _cursor(after, U)
@@ -1014,7 +1237,7 @@ def rank_corpus(news: Tensor, his_ids: Tensor, his_mask: Tensor, packed: Encoder
                         exclude_ids=None if excl is None else excl[u0:u1], eligible=ok, news_ids=sub,
                         news_bias=None if pri is None else pri.users(u0, u1), news_cluster=caps,
                         after=None if cur is None else cur.users(u0, u1), interest_cap=interest_cap,
-                        return_interest=return_interest)
+                        return_interest=return_interest, resume=None if walk is None else walk.users(u0, u1))
         for dst, src in zip(res, got):
             dst[u0:u1] = src
     return res

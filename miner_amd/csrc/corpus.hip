@@ -469,6 +469,10 @@ struct RkParams {
   int32_t* top_g;          // INT: the dominant interests out — pair form [U][M] next to the scores; capped form
   int icap;                //      [U][topk] next to the list (NULL: not wanted). icap > 0: the per-interest cap
                            //      as the caller gave it; the kernel reads it as `cap` (rk_run), as the capped form does
+  const int32_t* use_g;    // CAP | AFT, the resumed walk: per user the groups already served, [U][Q] strictly ascending,
+  const int32_t* use_c;    //      their counts [U][Q] (< 0 reads as 0) and the number of pairs [U] (clamped into
+  const int32_t* use_n;    //      [0, Q] on the device); a group's in-list rank starts at its count instead of 0
+  int Q;
 };
 
 // S > 1 (S = 8, grid = 256): the news steps are dealt to S slices (step st of slice s is news step
@@ -582,7 +586,7 @@ struct RkLds {
 // lists, counts and pair scores agree bit for bit with "scores + prior" in fp32. A compile-time
 // switch for the reason FLT is one: the unbiased instantiations are the same code as without it.
 // AFT: the cursor form (RkParams aft_s / aft_i; kRank, GEO 0, filtered — either filter may be null —,
-// split or unsplit, never CAP). A compile-time switch on the biased instantiation with the prior
+// split or unsplit; with CAP only as the resumed walk, below). A compile-time switch on the biased instantiation with the prior
 // tested at run time (the CAP pattern): as a run-time test on p.aft_s in the filtered instantiations
 // the filtered config-5 step without a cursor measured 81.27 against the parent's 80.39 ms, outside
 // the parent's own 0.74 ms spread (the two cursor words live in scalar registers across the step
@@ -613,6 +617,21 @@ struct RkLds {
 // double buffered) and read by the capped merge in place of its table loads; the list's groups leave
 // with the list (top_g, when wanted). Never for the mean score, which has no dominant interest (the
 // INT forms are not instantiated for it).
+// CAP | AFT (with or without INT): the resumed capped walk (RkParams use_g / use_c / use_n / Q next to
+// the cursor). The walk of the capped form continued strictly after the cursor, with used(g) entries
+// of group g already served: an entry is kept iff its group is negative or used(g) + (the better kept
+// entries of g in this call) < cap. "Keep the best cap - used(g) of group g" is a mergeable summary as
+// the capped list is, so the epilogue is the cursor form's (the AFT test on the ranked value and the
+// table id) and the capped merge changes in one place: a staged entry's in-group rank starts at
+// used(its group) instead of 0 (list entries carry theirs). used() is a lower-bound search of the
+// user's strictly ascending group table in global memory (L2-resident, at most 8 KB per user; at
+// K = 64, d = 768 with CAP | INT 8 KB of LDS remain, which two users x 1,024 pairs do not fit), made
+// by the merging wave where it loads the staged entries' cluster ids — nothing else of that wave is
+// in flight there —, at most 11 dependent loads per merge whatever the number of staged entries, and
+// skipped wholesale for an empty table. The table pointer and its length are per (tile, user), set in
+// the tile loop next to the cursor words: a workgroup's later tiles never read an earlier tile's.
+// Compile-time forms of their own: every instantiation a call without a state launches is the code
+// it was.
 constexpr int kRank = 0, kCount = 1, kPair = 2;
 constexpr int kMaxT = MINER_CORPUS_MAX_TARGETS;
 
@@ -636,7 +655,7 @@ struct RkForm {
   static constexpr int S = F & kFSplit ? kSplit : 1, GEO = F & kFGeo1 ? 1 : 0;
   static constexpr int NCH = F & kFD768 ? 768 * 2 / kRB<GEO> : 0, KC = F & kFK64 ? 64 : 0;   // KC: K compile-time (0: run time)
   static_assert(F < 2 * kFInt && (F & (kFCount | kFPair)) != (kFCount | kFPair) && (!(F & kFK64) || (F & kFD768)), "a form");
-  static_assert(!AFT || (MODE == kRank && GEO == 0 && FLT && BIAS && !CAP), "the cursor form: filtered, on the biased form, uncapped");
+  static_assert(!AFT || (MODE == kRank && GEO == 0 && FLT && BIAS), "the cursor form: filtered, on the biased form (with CAP: the resumed walk)");
   static_assert(!CAP || (MODE == kRank && S == 1 && GEO == 0 && FLT && BIAS), "the capped form: unsplit, filtered, on the biased form");
   static_assert(!INT || MODE == kPair || CAP, "the interest forms: the pair form and the capped form");
   static_assert(!SUB || (FLT && GEO == 0), "the subset form: a filtered form with one chunk in flight");
@@ -810,6 +829,12 @@ __global__ __launch_bounds__(kThreads) void rk_fused(RkParams p) {
   if (wave >= 4) __builtin_amdgcn_s_setprio(1);   // static priority for the second half (-0.8 %)
   if (threadIdx.x < 3 * kUT) cnt[threadIdx.x] = 0;
 
+  // CAP | AFT: the served-group table of this wave's user in the tile being computed (set in the tile
+  // loop, read by the merges of that tile only)
+  [[maybe_unused]] int use_n = 0;
+  [[maybe_unused]] const int32_t* use_g = nullptr;
+  [[maybe_unused]] const int32_t* use_c = nullptr;
+
   // merge the candidates staged in buffer `buf` into user uu's running top-k (one wave). The list
   // (best first) and the staged entries are ranked in parallel: an entry's new position is the
   // number of entries of both sets better than it (a total order on distinct news ids); entries
@@ -855,6 +880,32 @@ __global__ __launch_bounds__(kThreads) void rk_fused(RkParams p) {
         if constexpr (INT) sg[v] = lane + 64 * v < ns ? mg[j] : -1;
         else sg[v] = lane + 64 * v < ns ? p.clus[sid[v]] : -1;   // a staged id is a table row: inside [0, N)
         src[v] = 0;
+      }
+      if constexpr (AFT) {
+        // the resumed walk: src starts at used(sg) — the lower bound of sg in the user's ascending
+        // group table, the same number of steps for every lane (the range halves each time, so
+        // floor(log2 use_n) + 1 steps empty it), every address clamped into [0, use_n)
+        if (use_n > 0) {
+          int lo[kST], hi[kST];
+#pragma unroll
+          for (int v = 0; v < kST; ++v) { lo[v] = 0; hi[v] = use_n; }
+          for (int it = 0; (use_n >> it) > 0; ++it) {
+#pragma unroll
+            for (int v = 0; v < kST; ++v) {
+              const int mid = min((lo[v] + hi[v]) >> 1, use_n - 1);
+              const int gm = use_g[mid];
+              if (lo[v] < hi[v]) {
+                if (gm < sg[v]) lo[v] = mid + 1; else hi[v] = mid;
+              }
+            }
+          }
+#pragma unroll
+          for (int v = 0; v < kST; ++v) {
+            const int at = min(lo[v], use_n - 1);
+            const int gm = use_g[at], cm = use_c[at];
+            if (sg[v] >= 0 && lo[v] < use_n && gm == sg[v]) src[v] = max(cm, 0);
+          }
+        }
       }
 #pragma unroll
       for (int t = 0; t < kLT; ++t) {
@@ -1080,6 +1131,14 @@ __global__ __launch_bounds__(kThreads) void rk_fused(RkParams p) {
       const int au = min(ti * kUT + uu, p.U - 1);
       aft_s = __uint_as_float(rk_sload(reinterpret_cast<const uint32_t*>(p.aft_s) + au));
       aft_i = (int)rk_sload(reinterpret_cast<const uint32_t*>(p.aft_i) + au);
+      if constexpr (CAP) {
+        // the resumed walk: this tile's user's group table, its length a wave-uniform word clamped
+        // into [0, Q] so that no address leaves the table (a user past U: the last user's, never read
+        // — it stages nothing)
+        use_n = min(max((int)rk_sload(reinterpret_cast<const uint32_t*>(p.use_n) + au), 0), p.Q);
+        use_g = p.use_g + (size_t)au * p.Q;
+        use_c = p.use_c + (size_t)au * p.Q;
+      }
     }
     for (int sl = 0; sl < nsteps; ++sl) {
       const int st = news_step(sl);
@@ -1549,6 +1608,136 @@ __global__ __launch_bounds__(64 * kMergeUsers) void topk_merge(const float* __re
   }
 }
 
+// The state of a resumed capped walk advanced by one served page, one wave per user: the cursor that
+// continues the page (page_cursor's rule: the row's last entry if it is full, else (-inf, 2^31 - 1))
+// and the union of the served-group table with the groups of the page's entries, counts summed,
+// strictly ascending. An entry's group is pg[u][j] when given, else clus[id] for an id inside
+// [0, n_clus); an entry with id < 0 or a negative group adds nothing. The in table is ascending and
+// distinct (the precondition), so only the page is ranked by counting: a page entry leads its group
+// if no earlier entry of the page has it; a leader found in the in table (binary search, in LDS) adds
+// its multiplicity to that pair, a new leader goes to (the in pairs below it) + (the new leaders below
+// it), and an in pair moves up by the new leaders below it. More than Q pairs: overflow[u] = 1, the
+// cursor becomes "after everything" (the walk ends rather than ever breaking a cap) and the Q lowest
+// groups are written. Every LDS write is followed by a wave barrier before it is read.
+constexpr int kMaxWalk = MINER_CORPUS_MAX_WALK_GROUPS;
+__global__ __launch_bounds__(64 * kMergeUsers) void walk_advance(const float* __restrict__ ps, const int32_t* __restrict__ pi,
+                                                                 const int32_t* __restrict__ pg,
+                                                                 const int32_t* __restrict__ clus, int n_clus,
+                                                                 const int32_t* __restrict__ in_g,
+                                                                 const int32_t* __restrict__ in_c,
+                                                                 const int32_t* __restrict__ in_n, int Qin,
+                                                                 float* __restrict__ out_as, int32_t* __restrict__ out_ai,
+                                                                 int32_t* __restrict__ out_g, int32_t* __restrict__ out_c,
+                                                                 int32_t* __restrict__ out_n, uint8_t* __restrict__ overflow,
+                                                                 int U, int k, int Q) {
+  constexpr int kPT = kMaxTopk / 64, kQT = kMaxWalk / 64;
+  __shared__ int tg[kMergeUsers][kMaxWalk];     // the in table's groups
+  __shared__ int ta[kMergeUsers][kMaxWalk];     // what the page adds to each in pair
+  __shared__ int eg[kMergeUsers][kMaxTopk];     // the page entries' groups (-1: none), then -1 unless a NEW leader
+  const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int user = blockIdx.x * kMergeUsers + w;
+  if (user >= U) return;                   // wave-uniform; no block barrier below
+  const int nin = Qin > 0 ? min(max(in_n[user], 0), Qin) : 0;
+  int g[kPT], mult[kPT];
+  bool lead[kPT];
+#pragma unroll
+  for (int t = 0; t < kPT; ++t) {
+    const int j = lane + 64 * t;
+    g[t] = -1;
+    if (j < k) {
+      const int id = pi[(size_t)user * k + j];
+      if (id >= 0) {
+        if (pg != nullptr) g[t] = max(pg[(size_t)user * k + j], -1);
+        else if (id < n_clus) g[t] = max(clus[id], -1);
+      }
+    }
+    eg[w][j] = g[t];
+    mult[t] = 0;
+    lead[t] = g[t] >= 0;
+  }
+#pragma unroll
+  for (int q = 0; q < kQT; ++q) {
+    const int i = lane + 64 * q;
+    tg[w][i] = i < nin ? in_g[(size_t)user * Qin + i] : 0x7fffffff;
+    ta[w][i] = 0;
+  }
+  __builtin_amdgcn_s_waitcnt(0);
+  __builtin_amdgcn_wave_barrier();
+  // a page entry's multiplicity and whether it leads its group
+  for (int j2 = 0; j2 < k; ++j2) {
+    const int g2 = eg[w][j2];
+    if (g2 < 0) continue;                  // wave-uniform
+#pragma unroll
+    for (int t = 0; t < kPT; ++t) {
+      mult[t] += g[t] == g2 ? 1 : 0;
+      if (g[t] == g2 && j2 < lane + 64 * t) lead[t] = false;
+    }
+  }
+  // a leader's lower bound in the in table: found -> it adds to that pair; else a new group
+  int below[kPT];
+  bool fresh[kPT];
+#pragma unroll
+  for (int t = 0; t < kPT; ++t) {
+    int lo = 0, hi = nin;
+    while (lo < hi) {
+      const int mid = (lo + hi) >> 1;
+      if (tg[w][mid] < g[t]) lo = mid + 1; else hi = mid;
+    }
+    below[t] = lo;
+    const bool found = lead[t] && lo < nin && tg[w][lo] == g[t];
+    fresh[t] = lead[t] && !found;
+    if (found) ta[w][lo] = mult[t];        // one leader per group: no two lanes write one slot
+  }
+  __builtin_amdgcn_s_waitcnt(0);
+  __builtin_amdgcn_wave_barrier();          // every read of the page groups comes before this rewrite
+#pragma unroll
+  for (int t = 0; t < kPT; ++t) eg[w][lane + 64 * t] = fresh[t] ? g[t] : -1;
+  __builtin_amdgcn_s_waitcnt(0);
+  __builtin_amdgcn_wave_barrier();
+  // positions: the new leaders below each new leader and below each in pair
+  int ig[kQT], up[kQT], nb[kPT];
+#pragma unroll
+  for (int q = 0; q < kQT; ++q) { ig[q] = tg[w][lane + 64 * q]; up[q] = 0; }
+#pragma unroll
+  for (int t = 0; t < kPT; ++t) nb[t] = 0;
+  int nnew = 0;
+  for (int j2 = 0; j2 < k; ++j2) {
+    const int g2 = eg[w][j2];
+    if (g2 < 0) continue;                  // wave-uniform
+    ++nnew;
+#pragma unroll
+    for (int t = 0; t < kPT; ++t) nb[t] += g2 < g[t] ? 1 : 0;
+#pragma unroll
+    for (int q = 0; q < kQT; ++q) up[q] += g2 < ig[q] ? 1 : 0;
+  }
+  const int total = nin + nnew;
+  const bool over = total > Q;
+#pragma unroll
+  for (int q = 0; q < kQT; ++q) {
+    const int i = lane + 64 * q, pos = i + up[q];
+    if (i < nin && pos < Q) {
+      out_g[(size_t)user * Q + pos] = ig[q];
+      out_c[(size_t)user * Q + pos] = max(in_c[(size_t)user * Qin + i], 0) + ta[w][i];
+    }
+  }
+#pragma unroll
+  for (int t = 0; t < kPT; ++t) {
+    const int pos = below[t] + nb[t];
+    if (fresh[t] && pos < Q) {
+      out_g[(size_t)user * Q + pos] = g[t];
+      out_c[(size_t)user * Q + pos] = mult[t];
+    }
+  }
+  if (lane == 0) {
+    const int last = pi[(size_t)user * k + k - 1];
+    const bool full = last >= 0 && !over;
+    out_as[user] = full ? ps[(size_t)user * k + k - 1] : -INFINITY;
+    out_ai[user] = full ? last : 0x7fffffff;
+    out_n[user] = min(total, Q);
+    overflow[user] = over ? 1 : 0;
+  }
+}
+
 // every list empty: (-inf, -1) (the subset form with an empty id list)
 __global__ __launch_bounds__(256) void rk_fill_empty(float* __restrict__ top_s, int32_t* __restrict__ top_i,
                                                      int32_t* __restrict__ top_g, size_t n) {
@@ -1615,6 +1804,8 @@ constexpr unsigned kRkForms[] = {
     kFCapped, kFCapped | kFSub, kFCount, kFCount | kFBias, kFPairs, kFPairs | kFBias,
     // the interest forms (never instantiated for the mean score: rk_pick)
     kFPairs | kFInt, kFPairs | kFBias | kFInt, kFCapped | kFInt, kFCapped | kFSub | kFInt,
+    // the resumed capped walks: the capped forms with the cursor and the served-group table
+    kFCapped | kFAft, kFCapped | kFAft | kFSub, kFCapped | kFAft | kFInt, kFCapped | kFAft | kFSub | kFInt,
 #ifdef MINER_RK_GEO1
     kFGeo1, kFGeo1 | kFFlt, kFGeo1 | kFSplit, kFGeo1 | kFSplit | kFFlt,
 #endif
@@ -1629,9 +1820,11 @@ unsigned rk_form(const RkParams& prm, int mode, [[maybe_unused]] int dtype) {
   // the id list: one instantiation per shape of every form below, table or subset
   const unsigned sub = prm.ids != nullptr ? kFSub : 0;
   // the capped form — two kernels per shape (table / subset), not four. A workspace is never written.
-  if (prm.clus != nullptr) return kFCapped | sub;
+  // (the resumed instantiation only with a served-group table: a capped call without one launches what it did)
+  const unsigned res = prm.use_g != nullptr ? kFAft : 0;
+  if (prm.clus != nullptr) return kFCapped | sub | res;
   // the interest-capped form: the capped form with the group taken from the epilogue
-  if (prm.icap > 0) return kFCapped | kFInt | sub;
+  if (prm.icap > 0) return kFCapped | kFInt | sub | res;
   const unsigned split = rk_split(prm) ? kFSplit : 0;
   if (prm.aft_s != nullptr) return kFCursor | sub | split;
   if (prm.bias != nullptr) return kFBiased | sub | split;
@@ -1777,17 +1970,28 @@ int rk_run(void* stream, int dtype, RkParams prm, void* workspace, size_t worksp
   if (!aligned4(prm.clus)) return MINER_EALIGN;
   // the cursor: both words or neither, never with caps (a capped walk also needs the earlier pages'
   // per-cluster counts, which a (score, id) pair does not carry)
+  // (a served-group table — miner_rank_topk_resume — carries those counts and lifts the refusal)
+  const bool resume = prm.use_g != nullptr || prm.use_c != nullptr || prm.use_n != nullptr;
   if ((prm.aft_s == nullptr) != (prm.aft_i == nullptr)) return MINER_EINVAL;
-  if (prm.aft_s != nullptr && prm.clus != nullptr) return MINER_EINVAL;
+  if (prm.aft_s != nullptr && prm.clus != nullptr && !resume) return MINER_EINVAL;
   if (!aligned4(prm.aft_s) || !aligned4(prm.aft_i)) return MINER_EALIGN;
   // the per-interest cap: the capped form's restrictions (no cluster table beside it, no cursor), a
   // score type that has a dominant interest, and the interests out only under a cap
   if (prm.icap < 0) return MINER_EINVAL;
   if (prm.icap > kMaxTopk) return MINER_ESHAPE;
-  if (prm.icap > 0 && (prm.clus != nullptr || prm.aft_s != nullptr)) return MINER_EINVAL;
+  if (prm.icap > 0 && (prm.clus != nullptr || (prm.aft_s != nullptr && !resume))) return MINER_EINVAL;
   if (prm.icap > 0 && prm.score_type == MINER_SCORE_MEAN) return MINER_EINVAL;
   if (prm.icap == 0 && prm.top_g != nullptr) return MINER_EINVAL;
   if (!aligned4(prm.top_g)) return MINER_EALIGN;
+  // the resumed walk: a cursor, exactly one kind of cap (both at once has answered above), the whole
+  // table triple, its capacity and alignment
+  if (resume) {
+    if (prm.aft_s == nullptr) return MINER_EINVAL;
+    if (prm.clus == nullptr && prm.icap == 0) return MINER_EINVAL;
+    if (prm.Q < 0 || prm.use_g == nullptr || prm.use_c == nullptr || prm.use_n == nullptr) return MINER_EINVAL;
+    if (prm.Q > MINER_CORPUS_MAX_WALK_GROUPS) return MINER_ESHAPE;
+    if (!aligned4(prm.use_g) || !aligned4(prm.use_c) || !aligned4(prm.use_n)) return MINER_EALIGN;
+  }
   if (prm.U == 0) return MINER_OK;
   if (!aligned16(workspace)) return MINER_EALIGN;
   if (subset && prm.M == 0) {              // nothing to rank: every list empty, no ranker launch
@@ -2036,8 +2240,54 @@ int miner_rank_topk_interest(void* stream, int dtype, int score_type, const void
   prm.bias = news_bias; prm.grp = user_group; prm.G = G;
   prm.clus = news_cluster; prm.cap = cap;
   prm.aft_s = after_scores; prm.aft_i = after_ids;
+  return miner_rank_topk_resume(stream, dtype, score_type, user_mui, user_proj, news, U, N, d, K, topk, exclude_ids, E,
+                                news_ok, news_ids, M, top_scores, top_ids, workspace, workspace_bytes, news_bias, G,
+                                user_group, news_cluster, cap, after_scores, after_ids, interest_cap, top_interest, nullptr,
+                                nullptr, nullptr, 0);
+}
+
+int miner_rank_topk_resume(void* stream, int dtype, int score_type, const void* user_mui, const void* user_proj,
+                           const void* news, int U, int N, int d, int K, int topk, const int32_t* exclude_ids, int E,
+                           const uint32_t* news_ok, const int32_t* news_ids, int M, float* top_scores, int32_t* top_ids,
+                           void* workspace, size_t workspace_bytes, const float* news_bias, int G,
+                           const int32_t* user_group, const int32_t* news_cluster, int cap, const float* after_scores,
+                           const int32_t* after_ids, int interest_cap, int32_t* top_interest, const int32_t* used_groups,
+                           const int32_t* used_counts, const int32_t* n_used, int Q) {
+  RkParams prm{};
+  prm.mui = user_mui; prm.proj = user_proj; prm.news = news; prm.top_s = top_scores; prm.top_i = top_ids;
+  prm.U = U; prm.N = N; prm.d = d; prm.K = K; prm.topk = topk; prm.score_type = score_type;
+  prm.excl = exclude_ids; prm.E = E; prm.ok = news_ok;
+  prm.ids = news_ids; prm.M = M;           // the whole table: a NULL list with M < 0
+  prm.bias = news_bias; prm.grp = user_group; prm.G = G;
+  prm.clus = news_cluster; prm.cap = cap;
+  prm.aft_s = after_scores; prm.aft_i = after_ids;
   prm.icap = interest_cap; prm.top_g = top_interest;
+  prm.use_g = used_groups; prm.use_c = used_counts; prm.use_n = n_used; prm.Q = Q;   // all NULL: no table, Q is not read
   return rk_run(stream, dtype, prm, workspace, workspace_bytes);
+}
+
+int miner_walk_advance(void* stream, const float* page_scores, const int32_t* page_ids, const int32_t* page_groups,
+                       const int32_t* news_cluster, int n_cluster, const int32_t* in_groups, const int32_t* in_counts,
+                       const int32_t* in_n_used, int Q_in, float* out_after_scores, int32_t* out_after_ids,
+                       int32_t* out_groups, int32_t* out_counts, int32_t* out_n_used, uint8_t* overflow, int U, int k,
+                       int Q) {
+  if (U < 0 || k <= 0 || Q < 0 || Q_in < 0) return MINER_EINVAL;
+  if (k > kMaxTopk || Q > kMaxWalk || Q_in > kMaxWalk) return MINER_ESHAPE;
+  if (!page_scores || !page_ids || !in_n_used || !out_after_scores || !out_after_ids || !out_n_used || !overflow)
+    return MINER_EINVAL;
+  if ((Q_in > 0 && (!in_groups || !in_counts)) || (Q > 0 && (!out_groups || !out_counts))) return MINER_EINVAL;
+  if (page_groups == nullptr && (news_cluster == nullptr || n_cluster <= 0)) return MINER_EINVAL;
+  if (!aligned4(page_scores) || !aligned4(page_ids) || !aligned4(page_groups) || !aligned4(news_cluster) ||
+      !aligned4(in_groups) || !aligned4(in_counts) || !aligned4(in_n_used) || !aligned4(out_after_scores) ||
+      !aligned4(out_after_ids) || !aligned4(out_groups) || !aligned4(out_counts) || !aligned4(out_n_used))
+    return MINER_EALIGN;
+  if (U == 0) return MINER_OK;
+  hipLaunchKernelGGL(walk_advance, dim3((U + kMergeUsers - 1) / kMergeUsers), dim3(64 * kMergeUsers), 0,
+                     static_cast<hipStream_t>(stream), page_scores, page_ids, page_groups, news_cluster, n_cluster, in_groups,
+                     in_counts, in_n_used, Q_in, out_after_scores, out_after_ids, out_groups, out_counts, out_n_used, overflow,
+                     U, k, Q);
+  const hipError_t e = hipGetLastError();
+  return e == hipSuccess ? MINER_OK : (int)e;
 }
 
 int miner_topk_merge(void* stream, const float* a_scores, const int32_t* a_ids, int ka, const float* b_scores,

@@ -1,0 +1,314 @@
+"""The resumed capped walk on the host: miner_rank_topk_resume and miner_walk_advance are exported and
+declared (miner_rank_topk_interest plus three pointers and Q; the ABI number is unchanged), their
+argument errors (include/miner_corpus.h) are answered with their codes, in their order, after
+miner_rank_topk_interest's own checks and before any launch — with U = 0 where the arguments are
+accepted, so nothing launches —, a call without a table returns what miner_rank_topk_interest
+returns, and the Python-side argument errors of resume= / WalkState / start_walk / advance_walk /
+rank_topk_deep_capped are raised before anything touches a device. The AddressSanitizer driver of
+the two entry points (tests/native/abi_errors_resume.cpp, a stand-alone program) runs as
+tests/test_corpus_after_host.py runs its own. No compute call is made (runs on CPU-only machines)."""
+import ctypes
+import dataclasses
+import inspect
+import os
+import subprocess
+
+import pytest
+import torch
+
+from miner_amd import _lib, build, corpus
+
+OK, EINVAL, ESHAPE, EALIGN = 0, -1, -2, -3
+F32, WEIGHTED, MEAN = _lib.DTYPE_F32, _lib.SCORE_WEIGHTED, _lib.SCORE_MEAN
+P = ctypes.c_void_p
+QM = 1024
+
+
+@pytest.fixture(scope="module")
+def lib():
+    if not os.path.exists(_lib.LIB_PATH):
+        build.build_library()
+    return _lib.lib()
+
+
+def p(v):
+    return None if v is None else P(v)
+
+
+def interest_args(*, aft_s=144, aft_i=160, clus=112, cap=2, icap=0, top_g=None, bias=None, G=0, grp=None, ids=None, M=-1,
+                  excl=16, E=2, ok=48, U=0, N=100, K=32, d=64, k=10, mui=16, proj=16, news=16, dtype=F32, st=WEIGHTED,
+                  out_s=32, out_i=64, ws=None):
+    return [None, dtype, st, p(mui), p(proj), p(news), U, N, d, K, k, p(excl), E, p(ok), p(ids), M, p(out_s), p(out_i), p(ws), 0,
+            p(bias), G, p(grp), p(clus), cap, p(aft_s), p(aft_i), icap, p(top_g)]
+
+
+def resume(lib, *, ug=176, uc=192, un=208, Q=8, **kw):
+    return lib.miner_rank_topk_resume(*interest_args(**kw), p(ug), p(uc), p(un), Q)
+
+
+def advance(lib, *, ps=16, pi=32, pg=None, clus=48, nc=100, ig=64, ic=80, inn=96, Qin=8, oas=112, oai=128, og=144, oc=160,
+            on=176, ov=193, U=0, k=10, Q=8):
+    return lib.miner_walk_advance(None, p(ps), p(pi), p(pg), p(clus), nc, p(ig), p(ic), p(inn), Qin, p(oas), p(oai), p(og),
+                                  p(oc), p(on), p(ov), U, k, Q)
+
+
+def test_symbols_and_signatures(lib):
+    raw = ctypes.CDLL(_lib.LIB_PATH)
+    I, V = ctypes.c_int, ctypes.c_void_p
+    for name in ("miner_rank_topk_resume", "miner_walk_advance"):
+        assert name in _lib.SIGNATURES
+        assert ctypes.cast(getattr(raw, name), ctypes.c_void_p).value
+    assert lib.miner_abi_version() == 6 == _lib.ABI_VERSION      # the entry points are additive
+    assert _lib.SIGNATURES["miner_rank_topk_resume"] == (I, _lib.SIGNATURES["miner_rank_topk_interest"][1] + [V, V, V, I])
+    assert _lib.SIGNATURES["miner_walk_advance"] == (I, [V] * 5 + [I] + [V] * 3 + [I] + [V] * 6 + [I] * 3)
+    assert corpus.MAX_WALK_GROUPS == QM
+    for name in ("rank_topk", "rank_corpus"):
+        prm = inspect.signature(getattr(corpus, name)).parameters
+        assert prm["resume"].kind is inspect.Parameter.KEYWORD_ONLY and prm["resume"].default is None, name
+    deep = inspect.signature(corpus.rank_topk_deep_capped).parameters
+    assert list(deep)[:4] == ["user_mui", "user_proj", "news", "topk"]
+    assert deep["resume"].default is None and deep["return_state"].default is False
+    for kw in ("score_type", "exclude_ids", "eligible", "news_ids", "news_bias", "user_group", "news_cluster", "cluster_cap",
+               "interest_cap", "return_interest"):
+        assert deep[kw].kind is inspect.Parameter.KEYWORD_ONLY, kw
+    assert list(inspect.signature(corpus.start_walk).parameters) == ["U", "device", "capacity"]
+    assert list(inspect.signature(corpus.advance_walk).parameters) == ["state", "page", "news_cluster"]
+    assert [f.name for f in dataclasses.fields(corpus.WalkState)] == ["scores", "ids", "groups", "counts", "n_used", "overflow"]
+    # not offered there
+    for name in ("merge_topk", "update_topk", "cap_topk", "rank_topk_deep", "rank_of", "score_pairs", "rescore_topk"):
+        assert "resume" not in inspect.signature(getattr(corpus, name)).parameters, name
+
+
+def test_no_table_is_the_interest_call(lib):
+    none = dict(ug=None, uc=None, un=None)
+    cases = [dict(), dict(aft_s=None, aft_i=None), dict(clus=None, cap=0), dict(clus=None, cap=0, icap=3),
+             dict(clus=None, cap=0, icap=3, aft_s=None, aft_i=None, top_g=224), dict(aft_s=146), dict(aft_i=None),
+             dict(clus=114, aft_s=None, aft_i=None), dict(cap=0, aft_s=None, aft_i=None), dict(icap=-1), dict(icap=257),
+             dict(clus=None, cap=0, icap=3, st=MEAN, aft_s=None, aft_i=None), dict(top_g=224, aft_s=None, aft_i=None),
+             dict(k=0), dict(K=65), dict(dtype=9), dict(mui=20), dict(E=257), dict(ids=18, M=4), dict(bias=80, G=0)]
+    for kw in cases:
+        for U in (0, 3):
+            for Q in (0, -5, QM + 7):                            # Q is not read without a table
+                assert resume(lib, U=U, Q=Q, **none, **kw) == lib.miner_rank_topk_interest(*interest_args(U=U, **kw)), kw
+    assert resume(lib, **none) == EINVAL                         # a cursor under caps is still refused
+    assert resume(lib, clus=None, cap=0, icap=3, **none) == EINVAL
+    assert resume(lib, aft_s=None, aft_i=None, **none) == OK
+
+
+def test_resume_argument_errors_in_order_before_any_launch(lib):
+    for U in (0, 3):                                             # with users too: still no launch
+        assert resume(lib, U=U, aft_s=None, aft_i=None) == EINVAL                # no cursor
+        assert resume(lib, U=U, aft_s=None, aft_i=None, ug=178, Q=QM + 1) == EINVAL   # ... before shape and alignment
+        assert resume(lib, U=U, clus=None, cap=0) == EINVAL                      # no cap of either kind
+        assert resume(lib, U=U, clus=None, cap=0, ug=178, Q=QM + 1) == EINVAL
+        assert resume(lib, U=U, icap=3) == EINVAL                                # both kinds of cap
+        assert resume(lib, U=U, Q=-1) == EINVAL
+        assert resume(lib, U=U, ug=None) == EINVAL                               # a NULL among the three
+        assert resume(lib, U=U, uc=None) == EINVAL
+        assert resume(lib, U=U, un=None) == EINVAL
+        assert resume(lib, U=U, ug=None, uc=None, Q=QM + 1) == EINVAL            # ... before the shape
+        assert resume(lib, U=U, Q=QM + 1) == ESHAPE
+        assert resume(lib, U=U, Q=QM + 1, uc=194) == ESHAPE                      # ... before the alignment
+        assert resume(lib, U=U, ug=178) == EALIGN
+        assert resume(lib, U=U, uc=194) == EALIGN
+        assert resume(lib, U=U, un=210) == EALIGN
+        assert resume(lib, U=U, clus=None, cap=0, icap=3, top_g=224, un=209) == EALIGN
+    # accepted argument sets: U = 0 returns after the validation, nothing launches
+    assert resume(lib) == OK
+    assert resume(lib, ug=180, uc=196, un=212, Q=QM) == OK       # 4-byte, not 16-byte, aligned; the limit
+    assert resume(lib, Q=0) == OK                                # an empty table
+    assert resume(lib, clus=None, cap=0, icap=3) == OK           # the interest cap
+    assert resume(lib, clus=None, cap=0, icap=3, top_g=224, st=_lib.SCORE_MAX) == OK
+    assert resume(lib, st=MEAN) == OK                            # the mean score under cluster caps
+    assert resume(lib, bias=80, G=3, grp=96, ids=16, M=5, ws=256) == OK
+    assert resume(lib, excl=None, E=0, ok=None) == OK
+
+
+def test_the_older_checks_still_come_first(lib):
+    bad = dict(ug=178, uc=None, Q=QM + 1)                        # the state invalid as well
+    assert resume(lib, dtype=9, **bad) == EINVAL
+    assert resume(lib, K=65, **bad) == ESHAPE
+    assert resume(lib, d=100, **bad) == ESHAPE
+    assert resume(lib, st=7, **bad) == EINVAL
+    assert resume(lib, U=-1, **bad) == EINVAL
+    assert resume(lib, N=0, **bad) == EINVAL
+    assert resume(lib, mui=None, **bad) == EINVAL
+    assert resume(lib, news=20, un=None) == EALIGN
+    assert resume(lib, k=corpus.MAX_TOPK + 1, **bad) == ESHAPE
+    assert resume(lib, E=corpus.MAX_L + 1, **bad) == ESHAPE
+    assert resume(lib, ok=50, un=None) == EALIGN
+    assert resume(lib, ids=18, M=4, un=None) == EALIGN
+    assert resume(lib, bias=82, G=1, un=None) == EALIGN
+    assert resume(lib, cap=corpus.MAX_TOPK + 1, **bad) == ESHAPE
+    assert resume(lib, cap=0, Q=QM + 1) == EINVAL
+    assert resume(lib, clus=114, un=None) == EALIGN
+    assert resume(lib, aft_i=None, Q=QM + 1) == EINVAL           # half a cursor
+    assert resume(lib, aft_s=146, un=None) == EALIGN
+    assert resume(lib, clus=None, cap=0, icap=-1, Q=QM + 1) == EINVAL
+    assert resume(lib, clus=None, cap=0, icap=corpus.MAX_TOPK + 1, **bad) == ESHAPE
+    assert resume(lib, clus=None, cap=0, icap=3, st=MEAN, Q=QM + 1) == EINVAL
+    assert resume(lib, top_g=224, Q=QM + 1) == EINVAL            # interests without their cap
+    assert resume(lib, clus=None, cap=0, icap=3, top_g=226, un=None) == EALIGN
+
+
+def test_walk_advance_argument_errors_in_order(lib):
+    for U in (0, 3):
+        assert advance(lib, U=-1) == EINVAL
+        for kw in (dict(k=0), dict(k=-1), dict(Q=-1), dict(Qin=-1)):
+            assert advance(lib, U=U, **kw) == EINVAL, kw
+        assert advance(lib, U=U, k=0, Q=QM + 1) == EINVAL        # before the shapes
+        for kw in (dict(k=corpus.MAX_TOPK + 1), dict(Q=QM + 1), dict(Qin=QM + 1)):
+            assert advance(lib, U=U, **kw) == ESHAPE, kw
+            assert advance(lib, U=U, ps=None, **kw) == ESHAPE    # before the pointers
+        for name in ("ps", "pi", "inn", "ig", "ic", "oas", "oai", "og", "oc", "on", "ov"):
+            assert advance(lib, U=U, **{name: None}) == EINVAL, name
+        assert advance(lib, U=U, clus=None) == EINVAL            # no group source
+        assert advance(lib, U=U, nc=0) == EINVAL
+        assert advance(lib, U=U, clus=None, ps=18) == EINVAL     # ... before the alignment
+        for name, v in (("ps", 18), ("pi", 34), ("pg", 226), ("clus", 50), ("ig", 66), ("ic", 82), ("inn", 98), ("oas", 114),
+                        ("oai", 130), ("og", 146), ("oc", 162), ("on", 178)):
+            assert advance(lib, U=U, **{name: v}) == EALIGN, name
+    assert advance(lib) == OK
+    assert advance(lib, pg=224, clus=None, nc=0) == OK           # groups given
+    assert advance(lib, pg=224) == OK                            # both: the given groups win
+    assert advance(lib, k=corpus.MAX_TOPK, Q=QM, Qin=QM) == OK
+    assert advance(lib, ig=None, ic=None, Qin=0, og=None, oc=None, Q=0, k=1) == OK   # empty tables
+    assert advance(lib, ig=68, ic=84, inn=100, og=148, oc=164, on=180, ov=194) == OK
+
+
+def good_state(U, Q=4):
+    return corpus.start_walk(U, "cpu", Q)
+
+
+def test_start_walk_on_cpu_tensors():
+    s = corpus.start_walk(4, "cpu")
+    assert s.scores.dtype == torch.float32 and s.ids.dtype == torch.int32 and s.scores.shape == s.ids.shape == (4,)
+    assert (s.scores == float("inf")).all() and (s.ids == -1).all()
+    assert s.groups.dtype == s.counts.dtype == s.n_used.dtype == torch.int32 and s.overflow.dtype == torch.uint8
+    assert s.groups.shape == s.counts.shape == (4, QM) and s.n_used.shape == s.overflow.shape == (4,)
+    assert not s.groups.any() and not s.counts.any() and not s.n_used.any() and not s.overflow.any()
+    assert s.capacity == QM and s.cursor[0] is s.scores and s.cursor[1] is s.ids
+    for cap in (0, 1, 8, QM):
+        assert corpus.start_walk(3, "cpu", capacity=cap).groups.shape == (3, cap)
+    assert corpus.start_walk(0, "cpu", 5).groups.shape == (0, 5)
+    part = s.users(1, 3)
+    assert isinstance(part, corpus.WalkState) and part.scores.shape == (2,) and part.groups.shape == (2, QM)
+    assert part.n_used.shape == part.overflow.shape == part.ids.shape == (2,)
+    for bad in (-1, QM + 1, 2.0, "8", True, None):
+        with pytest.raises(ValueError):
+            corpus.start_walk(3, "cpu", capacity=bad)
+
+
+def test_python_argument_errors():
+    U, K, d, N = 3, 4, 64, 50
+    mui = torch.zeros(U, K, d)
+    tab = torch.zeros(N, d)
+    L = 6
+    hid, mask = torch.zeros(U, L, dtype=torch.int32), torch.ones(U, L, dtype=torch.bool)
+    pk = corpus.EncoderWeights(torch.zeros(16, dtype=torch.uint8), torch.float32, d, 8, K, True)
+    clus = torch.arange(N) % 4
+    caps = dict(news_cluster=clus, cluster_cap=2)
+    calls = {
+        "rank_topk": lambda **kw: corpus.rank_topk(mui, mui, tab, 5, **kw),
+        "rank_corpus": lambda **kw: corpus.rank_corpus(tab, hid, mask, pk, 5, **kw),
+        "rank_topk_deep_capped": lambda **kw: corpus.rank_topk_deep_capped(mui, mui, tab, 300, **kw),
+    }
+    g = good_state(U)
+    rep = dataclasses.replace
+    wrong = [(g.scores, g.ids), "state", 3, rep(g, scores=g.scores.double()), rep(g, scores=g.scores[:2]),
+             rep(g, scores=g.scores[None, :]), rep(g, ids=g.ids.long()), rep(g, ids=g.ids[:2]), rep(g, ids=g.ids.float()),
+             rep(g, groups=g.groups.long()), rep(g, counts=g.counts.long()), rep(g, groups=g.groups[:, :3]),
+             rep(g, groups=g.groups[:2]), rep(g, groups=g.groups[0], counts=g.counts[0]), rep(g, n_used=g.n_used.long()),
+             rep(g, n_used=g.n_used[:2]), rep(g, overflow=g.overflow.bool()), rep(g, overflow=g.overflow[:2]),
+             rep(g, groups=[0] * U), good_state(U + 1),
+             rep(g, groups=torch.zeros(U, QM + 1, dtype=torch.int32), counts=torch.zeros(U, QM + 1, dtype=torch.int32))]
+    for name, call in calls.items():
+        for bad in wrong:
+            with pytest.raises(ValueError):
+                call(resume=bad, **caps)
+            with pytest.raises(ValueError):
+                call(resume=bad, interest_cap=2)
+        # well-formed, but not on a GPU: no CPU path
+        for good in (g, good_state(U, 0), good_state(U, QM)):
+            with pytest.raises(RuntimeError):
+                call(resume=good, **caps)
+            with pytest.raises(RuntimeError):
+                call(resume=good, interest_cap=2, score_type="max")
+        with pytest.raises(ValueError):
+            call(resume=g, interest_cap=2, score_type="mean")
+        with pytest.raises(ValueError):
+            call(resume=g, interest_cap=2, **caps)               # one kind of cap
+    for name in ("rank_topk", "rank_corpus"):
+        with pytest.raises(ValueError):
+            calls[name](resume=g)                                # resume without a cap
+        with pytest.raises(ValueError):
+            calls[name](resume=g, return_interest=True)
+        with pytest.raises(ValueError):
+            calls[name](resume=g, after=corpus.start_cursor(U, "cpu"), **caps)   # resume with after
+        with pytest.raises(ValueError):
+            calls[name](resume=g, after=corpus.start_cursor(U, "cpu"), interest_cap=2)
+        with pytest.raises(ValueError):
+            calls[name](after=corpus.start_cursor(U, "cpu"), **caps)             # after= under caps: as before
+    with pytest.raises(ValueError):
+        corpus.rank_topk_deep(mui, mui, tab, 300, **caps)                        # ... and so rank_topk_deep
+    deep = calls["rank_topk_deep_capped"]
+    for kw in (dict(), dict(return_interest=True), dict(news_cluster=clus), dict(cluster_cap=2), dict(return_interest=True, **caps),
+               dict(capacity=-1, **caps), dict(capacity=QM + 1, **caps), dict(capacity=2.0, interest_cap=2)):
+        with pytest.raises(ValueError):
+            deep(**kw)
+    for bad in (0, -1, 2.0, "5", True, None):
+        with pytest.raises(ValueError):
+            corpus.rank_topk_deep_capped(mui, mui, tab, bad, **caps)
+    with pytest.raises(RuntimeError):
+        deep(**caps)
+    with pytest.raises(RuntimeError):
+        deep(interest_cap=3, return_interest=True, capacity=64)
+
+
+def test_advance_walk_argument_errors():
+    U, k = 3, 5
+    g = good_state(U)
+    s, i = torch.zeros(U, k), torch.zeros(U, k, dtype=torch.int32)
+    clus = torch.arange(40) % 4
+    bad_calls = [
+        lambda: corpus.advance_walk(g, (s, i)),                              # a pair without a table
+        lambda: corpus.advance_walk(g, (s, i, i), news_cluster=clus),        # a triple with one
+        lambda: corpus.advance_walk((g.scores, g.ids), (s, i), news_cluster=clus),
+        lambda: corpus.advance_walk(dataclasses.replace(g, n_used=g.n_used.long()), (s, i), news_cluster=clus),
+        lambda: corpus.advance_walk(g, s, news_cluster=clus),
+        lambda: corpus.advance_walk(g, (s,), news_cluster=clus),
+        lambda: corpus.advance_walk(g, (s, i.float()), news_cluster=clus),
+        lambda: corpus.advance_walk(g, (i, i), news_cluster=clus),
+        lambda: corpus.advance_walk(g, (s[:2], i[:2]), news_cluster=clus),   # another number of users
+        lambda: corpus.advance_walk(g, (s, i[:, :3]), news_cluster=clus),
+        lambda: corpus.advance_walk(g, (s[:, :0], i[:, :0]), news_cluster=clus),
+        lambda: corpus.advance_walk(g, (torch.zeros(U, 257), torch.zeros(U, 257, dtype=torch.int32)), news_cluster=clus),
+        lambda: corpus.advance_walk(g, (s, i), news_cluster=clus.float()),
+        lambda: corpus.advance_walk(g, (s, i), news_cluster=clus[None, :]),
+        lambda: corpus.advance_walk(g, (s, i, i.float())),
+        lambda: corpus.advance_walk(g, (s, i, i[:, :3])),
+    ]
+    for n, call in enumerate(bad_calls):
+        with pytest.raises(ValueError):
+            call()
+    for call in (lambda: corpus.advance_walk(g, (s, i), news_cluster=clus), lambda: corpus.advance_walk(g, (s, i.long(), i)),
+                 lambda: corpus.advance_walk(good_state(U, 0), (s, i), news_cluster=clus.int())):
+        with pytest.raises(RuntimeError):                                    # well-formed: no CPU path
+            call()
+
+
+@pytest.fixture(scope="module")
+def driver():
+    try:
+        return build.build_asan_driver_resume()
+    except RuntimeError as e:                       # no ROCm toolchain in this environment
+        pytest.skip(f"asan build unavailable: {e}")
+
+
+def test_new_entry_points_under_asan(driver):
+    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=0:abort_on_error=0:halt_on_error=1")
+    res = subprocess.run([driver], capture_output=True, text=True, timeout=300, env=env)
+    out = res.stdout + res.stderr
+    assert "AddressSanitizer" not in out, out[-4000:]
+    assert res.returncode == 0, out[-4000:]
+    assert "0 failures" in res.stdout, out[-2000:]
