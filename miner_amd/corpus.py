@@ -62,6 +62,24 @@ def _code(dtype: torch.dtype) -> int:
         raise TypeError(f"unsupported dtype {dtype}: float32 (parity), bfloat16 or float16")
 
 
+def _is_int(t, dim: Optional[int] = None) -> bool:
+    """An integer tensor (not float, complex, bool), of ``dim`` dimensions if given."""
+    return isinstance(t, Tensor) and not (t.is_floating_point() or t.is_complex() or t.dtype == torch.bool) \
+        and (dim is None or t.dim() == dim)
+
+
+def _is_list(s, i, g=None) -> bool:
+    """Scores [U,k] and integer ids [U,k] (and integer interests [U,k], if given) of one shape."""
+    return isinstance(s, Tensor) and s.dim() == 2 and _is_int(i, 2) and i.shape == s.shape \
+        and (g is None or (_is_int(g, 2) and g.shape == s.shape))
+
+
+def _cap(cap, what: str) -> int:
+    if isinstance(cap, bool) or not isinstance(cap, int) or not 1 <= cap <= MAX_TOPK:
+        raise ValueError(f"{what} must be an int in [1, {MAX_TOPK}]")
+    return cap
+
+
 @dataclasses.dataclass
 class EncoderWeights:
     """miner_encoder_pack() output."""
@@ -153,13 +171,20 @@ def pack_eligible(mask: Tensor) -> Tensor:
     return _pack_bits(mask)
 
 
-def _eligible_words(eligible: Tensor, N: int) -> Tensor:
+def _is_mask(eligible, N: int) -> bool:
+    """eligible= for a table of N news: True for a bool [N] mask, False for pack_eligible's int32
+    words; anything else is an argument error."""
     words = (N + 31) // 32
-    if eligible.dim() == 1 and eligible.dtype == torch.bool and eligible.shape[0] == N:
-        return pack_eligible(eligible)
-    if eligible.dim() == 1 and eligible.dtype == torch.int32 and eligible.shape[0] == words:
-        return eligible.contiguous()
+    if isinstance(eligible, Tensor) and eligible.dim() == 1:
+        if eligible.dtype == torch.bool and eligible.shape[0] == N:
+            return True
+        if eligible.dtype == torch.int32 and eligible.shape[0] == words:
+            return False
     raise ValueError(f"eligible must be bool [{N}] or packed int32 [{words}] (pack_eligible)")
+
+
+def _eligible_words(eligible: Tensor, N: int) -> Tensor:
+    return pack_eligible(eligible) if _is_mask(eligible, N) else eligible.contiguous()
 
 
 @dataclasses.dataclass
@@ -175,21 +200,11 @@ def canonical_news_ids(news_ids: Tensor, N: int) -> NewsIdList:
     outside [0, N) dropped, sorted, repeats removed (on the device). rank_topk / rank_corpus /
     update_topk do this themselves; pass the result instead of the tensor to do it once."""
     _require_device(news_ids)
-    if not isinstance(news_ids, Tensor) or news_ids.dim() != 1 or news_ids.is_floating_point() \
-            or news_ids.is_complex() or news_ids.dtype == torch.bool:
+    if not _is_int(news_ids, 1):
         raise ValueError("news_ids must be a 1-D integer tensor")
     ids = news_ids.to(torch.int64)
     ids = torch.unique(ids[(ids >= 0) & (ids < N)], sorted=True)
     return NewsIdList(ids.to(torch.int32).contiguous(), N)
-
-
-def _news_id_list(news_ids, N: int) -> NewsIdList:
-    if isinstance(news_ids, NewsIdList):
-        _require_device(news_ids.ids)
-        if news_ids.N != N:
-            raise ValueError(f"the id list was made for a table of {news_ids.N} news, not {N}")
-        return news_ids
-    return canonical_news_ids(news_ids, N)
 
 
 @dataclasses.dataclass
@@ -209,11 +224,7 @@ class _Prior:
 
 def _prior(news_bias, user_group, U: int, N: int) -> Optional[_Prior]:
     """news_bias= / user_group= of the ranking entries -> a _Prior, or None without a prior. Shapes,
-    dtypes and the group values are checked before anything touches the device."""
-    if isinstance(news_bias, _Prior):
-        if user_group is not None:
-            raise ValueError("user_group is part of the checked prior")
-        return news_bias
+    dtypes and the group values are checked; that the tensors are on the device is the caller's check."""
     if news_bias is None:
         if user_group is not None:
             raise ValueError("user_group without news_bias")
@@ -226,12 +237,10 @@ def _prior(news_bias, user_group, U: int, N: int) -> Optional[_Prior]:
         if G > 1:
             raise ValueError(f"news_bias holds {G} rows: user_group [{U}] says which row a user reads")
     else:
-        if not isinstance(user_group, Tensor) or user_group.dim() != 1 or user_group.shape[0] != U \
-                or user_group.is_floating_point() or user_group.is_complex() or user_group.dtype == torch.bool:
+        if not _is_int(user_group, 1) or user_group.shape[0] != U:
             raise ValueError(f"user_group must be an integer [{U}] tensor")
         if U and (int(user_group.min()) < 0 or int(user_group.max()) >= G):
             raise ValueError(f"user_group out of range [0, {G})")
-    _require_device(news_bias, user_group)
     return _Prior(news_bias.reshape(G, N).contiguous(), _contig(user_group, torch.int32))
 
 
@@ -249,28 +258,18 @@ class _Caps:
 
 def _caps(news_cluster, cluster_cap, N: Optional[int]) -> Optional[_Caps]:
     """news_cluster= / cluster_cap= of the ranking and merging entries -> a _Caps, or None without
-    caps. Everything but the value range is checked before anything touches the device. ``N``: the
-    length the table must have (None: any, at least one entry — the merging entries)."""
-    if isinstance(news_cluster, _Caps):
-        if cluster_cap is not None:
-            raise ValueError("cluster_cap is part of the checked caps")
-        if N is not None and news_cluster.cluster.shape[0] != N:
-            raise ValueError(f"the cluster table was made for {news_cluster.cluster.shape[0]} news, not {N}")
-        return news_cluster
+    caps; that the table is on the device is the caller's check. ``N``: the length the table must
+    have (None: any, at least one entry — the merging entries)."""
     if news_cluster is None and cluster_cap is None:
         return None
     if news_cluster is None or cluster_cap is None:
         raise ValueError("news_cluster and cluster_cap go together")
-    if isinstance(cluster_cap, bool) or not isinstance(cluster_cap, int) or not 1 <= cluster_cap <= MAX_TOPK:
-        raise ValueError(f"cluster_cap must be an int in [1, {MAX_TOPK}]")
-    if not isinstance(news_cluster, Tensor) or news_cluster.dim() != 1 or news_cluster.is_floating_point() \
-            or news_cluster.is_complex() or news_cluster.dtype == torch.bool or news_cluster.shape[0] < 1 \
-            or (N is not None and news_cluster.shape[0] != N):
+    _cap(cluster_cap, "cluster_cap")
+    if not _is_int(news_cluster, 1) or news_cluster.shape[0] < 1 or (N is not None and news_cluster.shape[0] != N):
         raise ValueError("news_cluster must be a 1-D integer tensor" + (f" of {N} entries" if N is not None else ""))
     if news_cluster.dtype != torch.int32:
         if int(news_cluster.min()) < -2 ** 31 or int(news_cluster.max()) > 2 ** 31 - 1:
             raise ValueError("news_cluster values must fit int32")
-    _require_device(news_cluster)
     return _Caps(_contig(news_cluster, torch.int32), cluster_cap)
 
 
@@ -289,54 +288,21 @@ _INT32_MAX = 2 ** 31 - 1
 
 def _cursor(after, U: int) -> Optional[_Cursor]:
     """after= of the ranking entries -> a _Cursor, or None without one. Shapes and dtypes are checked
-    before anything touches the device; ids of a dtype wider than int32 must fit int32."""
+    (that the pair is on the device is the caller's check); ids of a dtype wider than int32 must fit int32."""
     if after is None:
         return None
-    if isinstance(after, _Cursor):
-        if after.scores.shape[0] != U:
-            raise ValueError(f"the cursor was made for {after.scores.shape[0]} users, not {U}")
-        return after
     try:
         s, i = after
     except (TypeError, ValueError):
         raise ValueError("after must be a (scores, ids) pair")
     if not isinstance(s, Tensor) or s.dtype != torch.float32 or s.dim() != 1 or s.shape[0] != U:
         raise ValueError(f"after: the scores must be a float32 [{U}] tensor")
-    if not isinstance(i, Tensor) or i.dim() != 1 or i.shape[0] != U or i.is_floating_point() or i.is_complex() \
-            or i.dtype == torch.bool:
+    if not _is_int(i, 1) or i.shape[0] != U:
         raise ValueError(f"after: the ids must be an integer [{U}] tensor")
     if i.dtype not in (torch.int32, torch.int16, torch.int8, torch.uint8) and U:
         if int(i.min()) < -2 ** 31 or int(i.max()) > _INT32_MAX:
             raise ValueError("after: the ids must fit int32")
-    _require_device(s, i)
     return _Cursor(s.contiguous(), _contig(i, torch.int32))
-
-
-def _no_cursor_under_caps(after, news_cluster, cluster_cap) -> None:
-    """A capped walk also needs the earlier pages' per-cluster counts, which a (score, id) pair does
-    not carry: a cursor together with caps is an argument error, whatever else is wrong with either."""
-    if after is not None and (news_cluster is not None or cluster_cap is not None):
-        raise ValueError("after= cannot be combined with news_cluster / cluster_cap")
-
-
-def _interest_args(interest_cap, return_interest, score_type, news_cluster=None, cluster_cap=None, after=None) -> int:
-    """interest_cap= / return_interest= of the ranking entries -> the C entries' interest_cap (0: none).
-    Everything is checked before anything touches the device: the mean score has no dominant
-    interest; a per-interest cap is an int in [1, MAX_TOPK] and, as the per-cluster caps, has no
-    cursor — and the two kinds of caps do not combine (one group per entry in the ranker's merge)."""
-    if interest_cap is None and not return_interest:
-        return 0
-    if score_type == "mean":
-        raise ValueError("score_type 'mean' has no dominant interest: interest_cap / return_interest need 'weighted' or 'max'")
-    if interest_cap is None:
-        return 0
-    if isinstance(interest_cap, bool) or not isinstance(interest_cap, int) or not 1 <= interest_cap <= MAX_TOPK:
-        raise ValueError(f"interest_cap must be an int in [1, {MAX_TOPK}]")
-    if news_cluster is not None or cluster_cap is not None:
-        raise ValueError("interest_cap cannot be combined with news_cluster / cluster_cap")
-    if after is not None:
-        raise ValueError("interest_cap cannot be combined with after= (there is no cursor under caps)")
-    return interest_cap
 
 
 def start_cursor(U: int, device):
@@ -355,8 +321,7 @@ def page_cursor(lists):
         s, i = lists
     except (TypeError, ValueError):
         raise ValueError("lists must be a (scores, ids) pair")
-    if not isinstance(s, Tensor) or not isinstance(i, Tensor) or s.dim() != 2 or s.shape != i.shape or s.shape[1] < 1 \
-            or not s.is_floating_point() or i.is_floating_point() or i.dtype == torch.bool:
+    if not _is_list(s, i) or s.shape[1] < 1 or not s.is_floating_point():
         raise ValueError("lists: scores [U,k] and integer ids [U,k] of one shape, k >= 1")
     last_s, last_i = s[:, -1].to(torch.float32), i[:, -1]
     full = last_i >= 0
@@ -396,10 +361,9 @@ class WalkState:
                          self.overflow[u0:u1])
 
 
-def _walk_state(state, U: Optional[int], on_device: bool = True) -> WalkState:
+def _walk_state(state, U: Optional[int]) -> WalkState:
     """resume= / advance_walk's state -> a checked WalkState with contiguous fields. Types, dtypes and
-    shapes are checked before anything touches the device (``on_device`` False: the caller checks
-    the device itself, after its other arguments)."""
+    shapes are checked; that the fields are on the device is the caller's check."""
     if not isinstance(state, WalkState):
         raise ValueError("resume must be a WalkState (start_walk, advance_walk)")
     fields = (state.scores, state.ids, state.groups, state.counts, state.n_used, state.overflow)
@@ -418,8 +382,6 @@ def _walk_state(state, U: Optional[int], on_device: bool = True) -> WalkState:
     if state.n_used.dtype != torch.int32 or tuple(state.n_used.shape) != (n,) or state.overflow.dtype != torch.uint8 \
             or tuple(state.overflow.shape) != (n,):
         raise ValueError(f"WalkState: n_used is int32 [{n}] and overflow uint8 [{n}]")
-    if on_device:
-        _require_device(*fields)
     return WalkState(*(t.contiguous() for t in fields))
 
 
@@ -443,8 +405,8 @@ def start_walk(U: int, device, capacity: int = MAX_WALK_GROUPS) -> WalkState:
 def advance_walk(state: WalkState, page, *, news_cluster=None) -> WalkState:
     """The state after ``page`` was served from ``state`` (miner_walk_advance: one small launch, no
     host synchronisation): the page's page_cursor, and the state's table plus the groups of the page's
-    entries — a (scores, ids) pair under ``news_cluster`` (the integer table, or rank_topk's checked
-    caps; an id at or past its length has no group), or a (scores, ids, interests) triple without it,
+    entries — a (scores, ids) pair under ``news_cluster`` (the integer table; an id at or past its
+    length has no group), or a (scores, ids, interests) triple without it,
     as rank_topk(interest_cap=, return_interest=True) returns. Tail entries and entries in no group
     add nothing. The new state has the old one's capacity; a user that would need more distinct
     groups gets overflow 1 and the cursor "after everything" (its next page is empty), and an
@@ -453,29 +415,25 @@ def advance_walk(state: WalkState, page, *, news_cluster=None) -> WalkState:
     triple = _is_triple(page)
     if triple == (news_cluster is not None):
         raise ValueError("advance_walk: a (scores, ids) page with news_cluster, or a (scores, ids, interests) page without")
-    st = _walk_state(state, None, on_device=False)
-    U, Q = st.groups.shape
-    if not triple:
-        try:
-            ps, pi = page
-        except (TypeError, ValueError):
-            raise ValueError("page must be a (scores, ids) pair or a (scores, ids, interests) triple")
-    else:
-        ps, pi = page[0], page[1]
-    if not isinstance(ps, Tensor) or not isinstance(pi, Tensor) or ps.dim() != 2 or ps.shape != pi.shape \
-            or not ps.is_floating_point() or pi.is_floating_point() or pi.dtype == torch.bool or ps.shape[0] != U \
-            or not 1 <= ps.shape[1] <= MAX_TOPK:
+    st = _walk_state(state, None)
+    U = st.groups.shape[0]
+    try:
+        ps, pi, pg = page if triple else (*page, None)
+    except (TypeError, ValueError):
+        raise ValueError("page must be a (scores, ids) pair or a (scores, ids, interests) triple")
+    if not _is_list(ps, pi) or not ps.is_floating_point() or ps.shape[0] != U or not 1 <= ps.shape[1] <= MAX_TOPK:
         raise ValueError(f"page: scores [{U},k] and integer ids [{U},k] of one shape, 1 <= k <= {MAX_TOPK}")
-    pg = clus = None
-    if triple:
-        pg = page[2]
-        if not isinstance(pg, Tensor) or pg.shape != ps.shape or pg.is_floating_point() or pg.is_complex() \
-                or pg.dtype == torch.bool:
-            raise ValueError("page: integer interests of the page's shape [U,k]")
-    else:
-        clus = _caps(news_cluster, None if isinstance(news_cluster, _Caps) else 1, None).cluster
-    _require_device(ps, pi, pg, st.scores, st.ids, st.groups, st.counts, st.n_used, st.overflow)
-    ps, pi, pg = _contig(ps, torch.float32), _contig(pi, torch.int32), _contig(pg, torch.int32)
+    if triple and not _is_list(ps, pi, pg):
+        raise ValueError("page: integer interests of the page's shape [U,k]")
+    clus = None if triple else _caps(news_cluster, 1, None).cluster
+    _require_device(ps, pi, pg, clus, *vars(st).values())
+    return _advance(st, _contig(ps, torch.float32), _contig(pi, torch.int32), _contig(pg, torch.int32), clus)
+
+
+def _advance(st: WalkState, ps: Tensor, pi: Tensor, pg: Optional[Tensor], clus: Optional[Tensor]) -> WalkState:
+    """advance_walk on checked arguments: the page fp32 / int32 [U,k] contiguous, its groups the
+    interests ``pg``, or else the clusters of the int32 table ``clus``."""
+    U, Q = st.groups.shape
     dev = ps.device
     k = ps.shape[1]
     out = WalkState(torch.empty(U, dtype=torch.float32, device=dev), torch.empty(U, dtype=torch.int32, device=dev),
@@ -492,16 +450,139 @@ def advance_walk(state: WalkState, page, *, news_cluster=None) -> WalkState:
     return out
 
 
-def _resume_args(resume, after, capped: bool, U: int) -> Optional[WalkState]:
-    """resume= of the ranking entries -> a checked WalkState, or None without one. A resumed walk
-    continues a capped list: it needs a cap, and it carries its own cursor."""
-    if resume is None:
-        return None
-    if after is not None:
+def _dominant_interest(score_type: str) -> None:
+    if score_type == "mean":
+        raise ValueError("score_type 'mean' has no dominant interest: interest_cap / return_interest need 'weighted' or 'max'")
+
+
+@dataclasses.dataclass(slots=True)      # (built on every call: the slots make that cheaper)
+class _Request:
+    """Everything a ranking call takes besides the user vectors, the table and topk — checked,
+    converted and on the device: the exclusions int32 [U,E] (None: none), the eligibility words, the
+    id list, the prior, the caps, the cursor and the walk state (a walk carries its own cursor),
+    icap (0: no per-interest cap), return_interest and the score type."""
+    excl: Optional[Tensor]
+    ok: Optional[Tensor]
+    sub: Optional[NewsIdList]
+    prior: Optional[_Prior]
+    caps: Optional[_Caps]
+    cursor: Optional[_Cursor]
+    walk: Optional[WalkState]
+    icap: int
+    return_interest: bool
+    score_type: str
+
+    def users(self, u0: int, u1: int) -> "_Request":
+        """The request of the users [u0, u1): what is per user is sliced, the rest shared."""
+        def cut(x):
+            return None if x is None else x[u0:u1] if isinstance(x, Tensor) else x.users(u0, u1)
+        # (once per batch: built directly, dataclasses.replace costs several times as much)
+        return _Request(cut(self.excl), self.ok, self.sub, cut(self.prior), self.caps, cut(self.cursor), cut(self.walk),
+                        self.icap, self.return_interest, self.score_type)
+
+
+def _request(U: int, N: int, *, score_type: str = "weighted", exclude_ids=None, eligible=None, news_ids=None,
+             news_bias=None, user_group=None, news_cluster=None, cluster_cap=None, after=None, interest_cap=None,
+             return_interest: bool = False, resume=None) -> _Request:
+    """The keyword options of the ranking entries, for U users and a table of N news -> a _Request.
+    The one place the options' combination rules live. Every argument error is raised before the
+    device check; the bitmap is packed and the id list canonicalised after it, once."""
+    capped = news_cluster is not None or cluster_cap is not None
+    icap = 0
+    if interest_cap is not None or return_interest:
+        _dominant_interest(score_type)
+    if interest_cap is not None:
+        # the capped form's restrictions: one group per entry in the ranker's merge, and no cursor
+        icap = _cap(interest_cap, "interest_cap")
+        if capped:
+            raise ValueError("interest_cap cannot be combined with news_cluster / cluster_cap")
+        if after is not None:
+            raise ValueError("interest_cap cannot be combined with after= (there is no cursor under caps)")
+    if after is not None and capped:
+        # a capped walk also needs the earlier pages' per-cluster counts, which a (score, id) pair does not carry
+        raise ValueError("after= cannot be combined with news_cluster / cluster_cap")
+    if resume is not None and after is not None:
         raise ValueError("resume= carries its own cursor: it cannot be combined with after=")
-    if not capped:
+    if resume is not None and not capped and not icap:
         raise ValueError("resume= continues a capped list: it needs news_cluster / cluster_cap or interest_cap")
-    return _walk_state(resume, U)
+    walk = None if resume is None else _walk_state(resume, U)
+    # (a checker is called only where its option is given: the plain call pays for none of them)
+    prior = None if news_bias is None and user_group is None else _prior(news_bias, user_group, U, N)
+    caps = _caps(news_cluster, cluster_cap, N) if capped else None
+    cursor = None if after is None else _cursor(after, U)
+    E = 0
+    if exclude_ids is not None:
+        if not _is_int(exclude_ids, 2) or exclude_ids.shape[0] != U:
+            raise ValueError(f"exclude_ids must be an integer [{U}, E] tensor")
+        E = exclude_ids.shape[1]
+        if E > MAX_L:
+            raise ValueError(f"exclude_ids holds {E} ids per user, more than {MAX_L}")
+    mask = eligible is not None and _is_mask(eligible, N)
+    listed = isinstance(news_ids, NewsIdList)
+    if listed and news_ids.N != N:
+        raise ValueError(f"the id list was made for a table of {news_ids.N} news, not {N}")
+    if news_ids is not None and not listed and not _is_int(news_ids, 1):
+        raise ValueError("news_ids must be a 1-D integer tensor")
+    _require_device(exclude_ids, eligible, news_ids.ids if listed else news_ids,
+                    *[t for x in (prior, caps, cursor, walk) if x is not None for t in vars(x).values()])
+    excl = ok = sub = None
+    if E:
+        excl = _contig(exclude_ids, torch.int32)
+    if eligible is not None:
+        ok = pack_eligible(eligible) if mask else eligible.contiguous()
+    if news_ids is not None:
+        sub = news_ids if listed else canonical_news_ids(news_ids, N)
+    return _Request(excl, ok, sub, prior, caps, cursor, walk, icap, return_interest, score_type)
+
+
+def _rank(mui: Tensor, proj: Optional[Tensor], tab: Tensor, topk: int, req: _Request):
+    """One ranked page for _rank_operands' user vectors and table under a request: (scores, ids), or
+    (scores, ids, interests) with req.return_interest. The one caller of the library's ranking entry
+    — the widest, miner_rank_topk_resume: what the request does not hold is NULL and launches the
+    narrower entry's kernel. Called by the public entries themselves (the warning's stack level)."""
+    U, K, d = mui.shape
+    N = tab.shape[0]
+    if not 1 <= topk <= MAX_TOPK:
+        raise ValueError(f"topk must be in [1, {MAX_TOPK}]")
+    icap, caps, walk, sub = req.icap, req.caps, req.walk, req.sub
+    if icap and topk > icap * K:
+        # the result is right, the step is slow (see rank_topk's docstring): say so once per call site
+        warnings.warn(f"rank_topk: topk={topk} exceeds interest_cap * K = {icap * K}: the list can never fill, so every "
+                      f"step merges all its news (several times the capped step); ask for topk <= {icap * K}",
+                      RuntimeWarning, stacklevel=3)
+    st, dt = _lib.SCORE_TYPES[req.score_type], _DT[mui.dtype]
+    dev = mui.device
+    top_s = torch.empty(U, topk, dtype=torch.float32, device=dev)
+    top_i = torch.empty(U, topk, dtype=torch.int32, device=dev)
+    top_g = torch.empty(U, topk, dtype=torch.int32, device=dev) if icap and req.return_interest else None
+    # a workspace only where the split form runs: the library's recommendation (U <= 510 on a 256-CU
+    # device), or MINER_RK_SPLIT=1 / 0 (read here, per call: a test / A/B switch) forcing either form
+    lib = _lib.lib()
+    force = os.environ.get("MINER_RK_SPLIT", "")
+    split = force == "1" if force in ("0", "1") else bool(lib.miner_rank_topk_split_recommended(U))
+    split = split and caps is None and icap == 0
+    nws = int(lib.miner_rank_topk_workspace_bytes(U, topk)) if split else 0
+    ws = torch.empty(nws, dtype=torch.uint8, device=dev) if nws else None
+    M = -1 if sub is None else sub.ids.numel()               # -1 with no list: the whole table
+    cur = req.cursor if walk is None else walk               # a walk carries its own cursor
+    # the served-group table: all NULL and Q = 0 without a walk (an empty [U, 0] table has no storage:
+    # any aligned non-NULL address stands for it, never read)
+    Q = 0 if walk is None else walk.capacity
+    used = (None, None, None) if walk is None else \
+        (_ptr(walk.groups if Q else walk.n_used), _ptr(walk.counts if Q else walk.n_used), _ptr(walk.n_used))
+    with torch.cuda.device(dev):
+        rc = lib.miner_rank_topk_resume(
+            _stream(dev), dt, st, _ptr(mui), _ptr(proj), _ptr(tab), U, N, d, K, topk,
+            _ptr(req.excl), 0 if req.excl is None else req.excl.shape[1], _ptr(req.ok),
+            _ptr(sub.ids) if M > 0 else None, M, _ptr(top_s), _ptr(top_i), _ptr(ws), nws, *_prior_args(req.prior),
+            None if caps is None else _ptr(caps.cluster), 0 if caps is None else caps.cap,
+            None if cur is None else _ptr(cur.scores), None if cur is None else _ptr(cur.ids), icap, _ptr(top_g), *used, Q)
+    _lib.check(rc, "miner_rank_topk")
+    if not req.return_interest:
+        return top_s, top_i
+    if top_g is None:        # no cap: the pair form on the listed ids (a tail id of -1 gives -1)
+        top_g = _score_pairs(st, dt, mui, proj, tab, top_i.to(torch.int64), None, True)[1]
+    return top_s, top_i, top_g
 
 
 def rank_topk(user_mui: Tensor, user_proj: Optional[Tensor], news: Tensor, topk: int, *,
@@ -586,68 +667,12 @@ def rank_topk(user_mui: Tensor, user_proj: Optional[Tensor], news: Tensor, topk:
     group — 'max' over a row whose M_k are all NaN scores -inf with interest -1 — is always kept, so
     a list can hold more than interest_cap · K entries). The price otherwise, 1.01 - 1.03x the
     capped step: profiles/rk_interest_ab.txt. With neither the call is today's."""
-    icap = _interest_args(interest_cap, return_interest, score_type, news_cluster, cluster_cap, after)
-    _no_cursor_under_caps(after, news_cluster, cluster_cap)
-    walk = _resume_args(resume, after, news_cluster is not None or cluster_cap is not None or icap > 0, user_mui.shape[0])
-    pri = _prior(news_bias, user_group, user_mui.shape[0], news.shape[0])
-    caps = _caps(news_cluster, cluster_cap, news.shape[0])
-    cur = _cursor(after, user_mui.shape[0]) if walk is None else _Cursor(walk.scores, walk.ids)
-    st, dt, mui, proj, tab = _rank_operands(user_mui, user_proj, news, score_type)
-    U, K, d = mui.shape
-    N = tab.shape[0]
-    if not 1 <= topk <= MAX_TOPK:
-        raise ValueError(f"topk must be in [1, {MAX_TOPK}]")
-    if icap and topk > icap * K:
-        # the result is right, the step is slow (see the docstring): say so once per call site
-        warnings.warn(f"rank_topk: topk={topk} exceeds interest_cap * K = {icap * K}: the list can never fill, so every "
-                      f"step merges all its news (several times the capped step); ask for topk <= {icap * K}",
-                      RuntimeWarning, stacklevel=2)
-    _require_device(exclude_ids, eligible)
-    excl, E = None, 0
-    if exclude_ids is not None:
-        if exclude_ids.dim() != 2 or exclude_ids.shape[0] != U or exclude_ids.is_floating_point() \
-                or exclude_ids.dtype == torch.bool:
-            raise ValueError(f"exclude_ids must be an integer [{U}, E] tensor")
-        E = exclude_ids.shape[1]
-        if E > MAX_L:
-            raise ValueError(f"exclude_ids holds {E} ids per user, more than {MAX_L}")
-        excl = _contig(exclude_ids, torch.int32) if E else None
-    ok = None if eligible is None else _eligible_words(eligible, N)
-    sub = None if news_ids is None else _news_id_list(news_ids, N)
-    dev = mui.device
-    top_s = torch.empty(U, topk, dtype=torch.float32, device=dev)
-    top_i = torch.empty(U, topk, dtype=torch.int32, device=dev)
-    # a workspace only where the split form runs: the library's recommendation (U <= 510 on a 256-CU
-    # device), or MINER_RK_SPLIT=1 / 0 (read here, per call: a test / A/B switch) forcing either form
-    lib = _lib.lib()
-    force = os.environ.get("MINER_RK_SPLIT", "")
-    split = force == "1" if force in ("0", "1") else bool(lib.miner_rank_topk_split_recommended(U))
-    split = split and caps is None and icap == 0
-    nws = int(lib.miner_rank_topk_workspace_bytes(U, topk)) if split else 0
-    ws = torch.empty(nws, dtype=torch.uint8, device=dev) if nws else None
-    M = -1 if sub is None else sub.ids.numel()               # -1 with no list: the whole table
-    top_g = torch.empty(U, topk, dtype=torch.int32, device=dev) if icap and return_interest else None
-    with torch.cuda.device(dev):
-        # the widest entry; what the call does not use is NULL and launches the narrower entry's kernel
-        args = (_stream(dev), dt, st, _ptr(mui), _ptr(proj), _ptr(tab), U, N, d, K, topk,
-                _ptr(excl), E, _ptr(ok), _ptr(sub.ids) if M > 0 else None, M, _ptr(top_s),
-                _ptr(top_i), _ptr(ws), nws, *_prior_args(pri),
-                None if caps is None else _ptr(caps.cluster), 0 if caps is None else caps.cap,
-                None if cur is None else _ptr(cur.scores), None if cur is None else _ptr(cur.ids),
-                icap, _ptr(top_g))
-        if walk is None:
-            rc = lib.miner_rank_topk_interest(*args)
-        else:
-            # (an empty [U, 0] table has no storage: any aligned non-NULL address stands for it, never read)
-            Q = walk.capacity
-            rc = lib.miner_rank_topk_resume(*args, _ptr(walk.groups) if Q else _ptr(walk.n_used),
-                                            _ptr(walk.counts) if Q else _ptr(walk.n_used), _ptr(walk.n_used), Q)
-    _lib.check(rc, "miner_rank_topk")
-    if not return_interest:
-        return top_s, top_i
-    if top_g is None:        # no cap: the pair form on the listed ids (a tail id of -1 gives -1)
-        top_g = _score_pairs(st, dt, mui, proj, tab, top_i.to(torch.int64), None, True)[1]
-    return top_s, top_i, top_g
+    req = _request(user_mui.shape[0], news.shape[0], score_type=score_type, exclude_ids=exclude_ids, eligible=eligible,
+                   news_ids=news_ids, news_bias=news_bias, user_group=user_group, news_cluster=news_cluster,
+                   cluster_cap=cluster_cap, after=after, interest_cap=interest_cap, return_interest=return_interest,
+                   resume=resume)
+    _, _, mui, proj, tab = _rank_operands(user_mui, user_proj, news, score_type)
+    return _rank(mui, proj, tab, topk, req)
 
 
 def rank_topk_deep(user_mui: Tensor, user_proj: Optional[Tensor], news: Tensor, topk: int, *, after=None,
@@ -669,29 +694,22 @@ def rank_topk_deep(user_mui: Tensor, user_proj: Optional[Tensor], news: Tensor, 
         raise ValueError("rank_topk_deep pages with cursors, and there is no cursor under news_cluster / cluster_cap")
     if interest_cap is not None:
         raise ValueError("rank_topk_deep pages with cursors, and there is no cursor under interest_cap")
-    _interest_args(None, return_interest, score_type)
     if isinstance(topk, bool) or not isinstance(topk, int) or topk < 1:
         raise ValueError("topk must be an int >= 1")
-    U, N = user_mui.shape[0], news.shape[0]
-    pri = _prior(news_bias, user_group, U, N)
-    cur = _cursor(after, U)
-    _require_device(user_mui, user_proj, news, exclude_ids, eligible)
-    ok = None if eligible is None else _eligible_words(eligible, N)
-    sub = None if news_ids is None else _news_id_list(news_ids, N)
-    dev = user_mui.device
-    top_s = torch.empty(U, topk, dtype=torch.float32, device=dev)
-    top_i = torch.empty(U, topk, dtype=torch.int32, device=dev)
-    top_g = torch.empty(U, topk, dtype=torch.int32, device=dev) if return_interest else None
+    U = user_mui.shape[0]
+    req = _request(U, news.shape[0], score_type=score_type, exclude_ids=exclude_ids, eligible=eligible, news_ids=news_ids,
+                   news_bias=news_bias, user_group=user_group, after=after, return_interest=return_interest)
+    _, _, mui, proj, tab = _rank_operands(user_mui, user_proj, news, score_type)
+    out = tuple(torch.empty(U, topk, dtype=dt, device=mui.device)
+                for dt in (torch.float32, torch.int32, torch.int32)[:3 if return_interest else 2])
     for k0 in range(0, topk, MAX_TOPK):
         k1 = min(topk, k0 + MAX_TOPK)
-        page = rank_topk(user_mui, user_proj, news, k1 - k0, score_type=score_type, exclude_ids=exclude_ids,
-                         eligible=ok, news_ids=sub, news_bias=pri, after=cur, return_interest=return_interest)
-        top_s[:, k0:k1], top_i[:, k0:k1] = page[:2]
-        if return_interest:
-            top_g[:, k0:k1] = page[2]
+        page = _rank(mui, proj, tab, k1 - k0, req)
+        for dst, src in zip(out, page):
+            dst[:, k0:k1] = src
         if k1 < topk:
-            cur = _Cursor(*page_cursor(page[:2]))
-    return (top_s, top_i, top_g) if return_interest else (top_s, top_i)
+            req = dataclasses.replace(req, cursor=_Cursor(*page_cursor(page[:2])))
+    return out
 
 
 def rank_topk_deep_capped(user_mui: Tensor, user_proj: Optional[Tensor], news: Tensor, topk: int, *, resume=None,
@@ -716,47 +734,40 @@ def rank_topk_deep_capped(user_mui: Tensor, user_proj: Optional[Tensor], news: T
     than a cap ever being broken; under interest_cap there are at most K <= 64 groups."""
     if isinstance(topk, bool) or not isinstance(topk, int) or topk < 1:
         raise ValueError("topk must be an int >= 1")
-    U, N = user_mui.shape[0], news.shape[0]
-    icap = _interest_args(interest_cap, return_interest, score_type, news_cluster, cluster_cap)
-    if (news_cluster is None and cluster_cap is None) == (icap == 0):
+    U = user_mui.shape[0]
+    if news_cluster is None and cluster_cap is None and interest_cap is None:      # (both kinds: _request's error)
         raise ValueError("rank_topk_deep_capped needs news_cluster / cluster_cap or interest_cap (one of them); "
                          "rank_topk_deep is the uncapped deep list")
-    if return_interest and not icap:
+    if return_interest and interest_cap is None:
         raise ValueError("return_interest: the interests are listed under interest_cap")
     Q = _capacity(capacity)
-    state = None if resume is None else _walk_state(resume, U)
-    pri = _prior(news_bias, user_group, U, N)
-    caps = _caps(news_cluster, cluster_cap, N)
-    _require_device(user_mui, user_proj, news, exclude_ids, eligible)
-    ok = None if eligible is None else _eligible_words(eligible, N)
-    sub = None if news_ids is None else _news_id_list(news_ids, N)
-    dev = user_mui.device
-    if state is None:
-        state = start_walk(U, dev, Q)
-    top_s = torch.empty(U, topk, dtype=torch.float32, device=dev)
-    top_i = torch.empty(U, topk, dtype=torch.int32, device=dev)
-    top_g = torch.empty(U, topk, dtype=torch.int32, device=dev) if return_interest else None
+    # (under interest_cap every page lists its interests: they are the groups advance_walk counts)
+    req = _request(U, news.shape[0], score_type=score_type, exclude_ids=exclude_ids, eligible=eligible, news_ids=news_ids,
+                   news_bias=news_bias, user_group=user_group, news_cluster=news_cluster, cluster_cap=cluster_cap,
+                   interest_cap=interest_cap, return_interest=interest_cap is not None, resume=resume)
+    _, _, mui, proj, tab = _rank_operands(user_mui, user_proj, news, score_type)
+    if req.walk is None:
+        req = dataclasses.replace(req, walk=start_walk(U, mui.device, Q))
+    clus = None if req.caps is None else req.caps.cluster
+    out = tuple(torch.empty(U, topk, dtype=dt, device=mui.device)
+                for dt in (torch.float32, torch.int32, torch.int32)[:3 if return_interest else 2])
     for k0 in range(0, topk, MAX_TOPK):
         k1 = min(topk, k0 + MAX_TOPK)
-        page = rank_topk(user_mui, user_proj, news, k1 - k0, score_type=score_type, exclude_ids=exclude_ids,
-                         eligible=ok, news_ids=sub, news_bias=pri, news_cluster=caps, interest_cap=interest_cap,
-                         return_interest=icap > 0, resume=state)
-        top_s[:, k0:k1], top_i[:, k0:k1] = page[:2]
-        if return_interest:
-            top_g[:, k0:k1] = page[2]
+        page = _rank(mui, proj, tab, k1 - k0, req)
+        for dst, src in zip(out, page):
+            dst[:, k0:k1] = src
         if k1 < topk or return_state:
-            state = advance_walk(state, page, news_cluster=caps)
-    res = (top_s, top_i, top_g) if return_interest else (top_s, top_i)
-    return res + (state,) if return_state else res
+            req = dataclasses.replace(req, walk=_advance(req.walk, page[0], page[1], None if req.caps else page[2], clus))
+    return out + (req.walk,) if return_state else out
 
 
 def _list_pair(lists, what: str):
+    """(scores, ids) -> the checked pair, fp32 and int32 [U,k]; that it is on the device is the caller's check."""
     try:
         s, i = lists
     except (TypeError, ValueError):
         raise ValueError(f"{what} must be a (scores, ids) pair")
-    _require_device(s, i)
-    if s.dim() != 2 or s.shape != i.shape or i.is_floating_point() or i.dtype == torch.bool:
+    if not _is_list(s, i):
         raise ValueError(f"{what}: scores [U,k] and integer ids [U,k] of one shape")
     if s.shape[1] > MAX_TOPK:
         raise ValueError(f"{what} is {s.shape[1]} wide, more than {MAX_TOPK}")
@@ -770,12 +781,9 @@ def _is_triple(lists) -> bool:
 def _list_triple(lists, what: str):
     """(scores, ids, interests) -> the checked pair plus the interests int32 [U,k]."""
     g = lists[2]
-    if not isinstance(g, Tensor) or not isinstance(lists[0], Tensor) or g.shape != lists[0].shape \
-            or g.is_floating_point() or g.is_complex() or g.dtype == torch.bool:
+    if not _is_int(g) or not isinstance(lists[0], Tensor) or g.shape != lists[0].shape:
         raise ValueError(f"{what}: integer interests of the lists' shape [U,k]")
-    s, i = _list_pair(lists[:2], what)
-    _require_device(g)
-    return s, i, _contig(g, torch.int32)
+    return *_list_pair(lists[:2], what), _contig(g, torch.int32)
 
 
 def merge_topk(a, b, topk: Optional[int] = None, *, eligible: Optional[Tensor] = None, news_cluster=None,
@@ -803,13 +811,13 @@ def merge_topk(a, b, topk: Optional[int] = None, *, eligible: Optional[Tensor] =
     if triple != _is_triple(b):
         raise ValueError("merge_topk: both lists are (scores, ids) pairs or both (scores, ids, interests) triples")
     if interest_cap is not None:
-        if isinstance(interest_cap, bool) or not isinstance(interest_cap, int) or not 1 <= interest_cap <= MAX_TOPK:
-            raise ValueError(f"interest_cap must be an int in [1, {MAX_TOPK}]")
+        _cap(interest_cap, "interest_cap")
         if not triple:
             raise ValueError("interest_cap needs (scores, ids, interests) triples")
     if triple and (news_cluster is not None or cluster_cap is not None):
         raise ValueError("lists with interests cannot be merged under news_cluster / cluster_cap")
     caps = _caps(news_cluster, cluster_cap, None)
+    _require_device(news_cluster)
     a_g = b_g = None
     if triple:
         a_s, a_i, a_g = _list_triple(a, "list a")
@@ -817,6 +825,7 @@ def merge_topk(a, b, topk: Optional[int] = None, *, eligible: Optional[Tensor] =
     else:
         a_s, a_i = _list_pair(a, "list a")
         b_s, b_i = _list_pair(b, "list b")
+    _require_device(a_s, a_i, a_g, b_s, b_i, b_g)
     U, ka = a_s.shape
     kb = b_s.shape[1]
     if b_s.shape[0] != U:
@@ -889,22 +898,21 @@ def update_topk(lists, user_mui: Tensor, user_proj: Optional[Tensor], news: Tens
     interests in ``lists`` are those of the user vectors it was ranked with.) ``resume=`` is not
     offered: ``lists`` is a first page (a capped list from the top), not a later page of a walk."""
     triple = _is_triple(lists)
-    icap = _interest_args(interest_cap, triple, score_type, news_cluster, cluster_cap)
-    if icap and not triple:
+    if interest_cap is not None and not triple:
         raise ValueError("interest_cap needs lists with interests: a (scores, ids, interests) triple")
     if triple and (news_cluster is not None or cluster_cap is not None):
         raise ValueError("lists with interests cannot be updated under news_cluster / cluster_cap")
-    pri = _prior(news_bias, user_group, user_mui.shape[0], news.shape[0])
-    caps = _caps(news_cluster, cluster_cap, news.shape[0])
     old = _list_triple(lists, "lists") if triple else _list_pair(lists, "lists")
     k = old[0].shape[1]
     if k < 1:
         raise ValueError("lists must hold at least one entry per user")
-    ok = None if eligible is None else _eligible_words(eligible, news.shape[0])
-    fresh = rank_topk(user_mui, user_proj, news, k, score_type=score_type, exclude_ids=exclude_ids, eligible=ok,
-                      news_ids=news_ids, news_bias=pri, news_cluster=caps, interest_cap=interest_cap,
-                      return_interest=triple)
-    return merge_topk(old, fresh, k, eligible=ok, news_cluster=caps, interest_cap=interest_cap)
+    req = _request(user_mui.shape[0], news.shape[0], score_type=score_type, exclude_ids=exclude_ids, eligible=eligible,
+                   news_ids=news_ids, news_bias=news_bias, user_group=user_group, news_cluster=news_cluster,
+                   cluster_cap=cluster_cap, interest_cap=interest_cap, return_interest=triple)
+    _, _, mui, proj, tab = _rank_operands(user_mui, user_proj, news, score_type)
+    fresh = _rank(mui, proj, tab, k, req)
+    return merge_topk(old, fresh, k, eligible=req.ok, news_cluster=None if req.caps is None else req.caps.cluster,
+                      cluster_cap=cluster_cap, interest_cap=interest_cap)
 
 
 def cap_topk(lists, news_cluster, cluster_cap: int, topk: Optional[int] = None):
@@ -916,10 +924,12 @@ def cap_topk(lists, news_cluster, cluster_cap: int, topk: Optional[int] = None):
     not full (then the input held every admissible news); a row that comes back short from a full
     input needs the capped ranker. Every group counts from 0: there is no ``resume=`` here."""
     caps = _caps(news_cluster, cluster_cap, None)
+    _require_device(news_cluster)
     s, i = _list_pair(lists, "lists")
     if s.shape[1] < 1:
         raise ValueError("lists must hold at least one entry per user")
-    return merge_topk((s[:, :0], i[:, :0]), (s, i), s.shape[1] if topk is None else topk, news_cluster=caps)
+    return merge_topk((s[:, :0], i[:, :0]), (s, i), s.shape[1] if topk is None else topk, news_cluster=caps.cluster,
+                      cluster_cap=caps.cap)
 
 
 MAX_TARGETS = 64
@@ -945,8 +955,7 @@ def _rank_operands(user_mui: Tensor, user_proj: Optional[Tensor], news: Tensor, 
 
 def _check_ids(ids, U: int, what: str) -> None:
     """Shape and dtype of an id matrix (before anything touches the device)."""
-    if not isinstance(ids, Tensor) or ids.dim() != 2 or ids.shape[0] != U or ids.is_floating_point() \
-            or ids.is_complex() or ids.dtype == torch.bool:
+    if not _is_int(ids, 2) or ids.shape[0] != U:
         raise ValueError(f"{what} must be an integer [{U}, C] tensor")
 
 
@@ -994,9 +1003,11 @@ def score_pairs(user_mui: Tensor, user_proj: Optional[Tensor], news: Tensor, can
     whose logit, or M_k under 'max', equals the maximum the score's reduction over K found; -1 for
     an id outside [0, N); ValueError under 'mean'), from the same launch: the scores keep their bits
     and the prior does not enter the interest."""
-    _interest_args(None, return_interest, score_type)
+    if return_interest:
+        _dominant_interest(score_type)
     _check_ids(cand_ids, user_mui.shape[0], "cand_ids")
     pri = _prior(news_bias, user_group, user_mui.shape[0], news.shape[0])
+    _require_device(news_bias, user_group)
     st, dt, mui, proj, tab = _rank_operands(user_mui, user_proj, news, score_type)
     return _score_pairs(st, dt, mui, proj, tab, _id_matrix(cand_ids, mui.shape[0], tab.shape[0], "cand_ids"), pri,
                         return_interest)
@@ -1007,7 +1018,8 @@ def _better(s: Tensor, i: Tensor, s2: Tensor, i2: Tensor) -> Tensor:
     return (s > s2) | ((s == s2) & (i < i2))
 
 
-def _rank_of(user_mui, user_proj, news, target_ids, score_type, exclude_ids, eligible, news_bias=None, user_group=None):
+def _rank_of(user_mui, user_proj, news, target_ids, score_type, exclude_ids, eligible, pri: Optional[_Prior] = None):
+    """rank_of under a checked prior, plus the number of news in each user's list (int64 [U])."""
     _check_ids(target_ids, user_mui.shape[0], "target_ids")
     if not 1 <= target_ids.shape[1] <= MAX_TARGETS:
         raise ValueError(f"target_ids holds {target_ids.shape[1]} targets per user, outside [1, {MAX_TARGETS}]")
@@ -1015,7 +1027,6 @@ def _rank_of(user_mui, user_proj, news, target_ids, score_type, exclude_ids, eli
         _check_ids(exclude_ids, user_mui.shape[0], "exclude_ids")
         if exclude_ids.shape[1] > MAX_L:
             raise ValueError(f"exclude_ids holds {exclude_ids.shape[1]} ids per user, more than {MAX_L}")
-    pri = _prior(news_bias, user_group, user_mui.shape[0], news.shape[0])
     st, dt, mui, proj, tab = _rank_operands(user_mui, user_proj, news, score_type)
     U, K, d = mui.shape
     N = tab.shape[0]
@@ -1075,9 +1086,9 @@ def rank_of(user_mui: Tensor, user_proj: Optional[Tensor], news: Tensor, target_
     its distinct, in-range, eligible ids that rank before the target are subtracted. ``news_bias`` /
     ``user_group`` as in rank_topk: targets, stream and correction all use the biased score, so the
     rank is exact under the prior too (a target whose biased score is NaN gets -1)."""
-    ranks, scores, _ = _rank_of(user_mui, user_proj, news, target_ids, score_type, exclude_ids, eligible, news_bias,
-                                user_group)
-    return ranks, scores
+    pri = _prior(news_bias, user_group, user_mui.shape[0], news.shape[0])
+    _require_device(news_bias, user_group)
+    return _rank_of(user_mui, user_proj, news, target_ids, score_type, exclude_ids, eligible, pri)[:2]
 
 
 def corpus_metrics(ranks: Tensor, n_ranked: Optional[Tensor] = None, *, ks=(5, 10)):
@@ -1132,7 +1143,9 @@ def rescore_topk(lists, user_mui: Tensor, user_proj: Optional[Tensor], news: Ten
     _, ids = _list_pair(lists, "lists")
     if ids.shape[1] < 1:
         raise ValueError("lists must hold at least one entry per user")
-    fresh = score_pairs(user_mui, user_proj, news, ids, score_type=score_type, news_bias=pri)
+    _require_device(news_bias, user_group)
+    st, dt, mui, proj, tab = _rank_operands(user_mui, user_proj, news, score_type)
+    fresh = _score_pairs(st, dt, mui, proj, tab, _id_matrix(ids, mui.shape[0], tab.shape[0], "lists"), pri)
     empty = (fresh[:, :0], ids[:, :0])
     return merge_topk(empty, (fresh, ids), ids.shape[1], eligible=eligible)
 
@@ -1168,12 +1181,12 @@ def evaluate_corpus(news: Tensor, his_ids: Tensor, his_mask: Tensor, packed: Enc
         raise ValueError("batch must be positive")
     U = his_ids.shape[0]
     dev = news.device
-    pri = _prior(news_bias, user_group, U, news.shape[0])
-    _require_device(news, his_ids, his_mask, target_ids, exclude_ids, eligible)
+    # the prior checked and the bitmap packed once (rank_of's exclusions are an id matrix of its own)
+    req = _request(U, news.shape[0], score_type=score_type, eligible=eligible, news_bias=news_bias, user_group=user_group)
+    _require_device(news, his_ids, his_mask, target_ids, exclude_ids)
     excl = _exclusions(exclude_ids, exclude_history, his_ids, his_mask)
     if target_ids.dim() != 2 or target_ids.shape[0] != U:
         raise ValueError(f"target_ids must be [{U}, T]")
-    ok = None if eligible is None else _eligible_words(eligible, news.shape[0])   # packed once
     ranks = torch.empty(U, target_ids.shape[1], dtype=torch.int32, device=dev)
     survivors = torch.empty(U, dtype=torch.int64, device=dev)
     with_proj = score_type == "weighted"
@@ -1182,8 +1195,8 @@ def evaluate_corpus(news: Tensor, his_ids: Tensor, his_mask: Tensor, packed: Enc
         mui, proj = encode_users(news, his_mask[u0:u1], packed, his_ids=his_ids[u0:u1],
                                  his_bias=None if his_bias is None else his_bias[u0:u1], with_proj=with_proj)
         ranks[u0:u1], _, survivors[u0:u1] = _rank_of(mui, proj, news, target_ids[u0:u1], score_type,
-                                                     None if excl is None else excl[u0:u1], ok,
-                                                     None if pri is None else pri.users(u0, u1))
+                                                     None if excl is None else excl[u0:u1], req.ok,
+                                                     None if req.prior is None else req.prior.users(u0, u1))
     return ranks, corpus_metrics(ranks, survivors, ks=ks)[1]
 
 
@@ -1213,18 +1226,15 @@ def rank_corpus(news: Tensor, his_ids: Tensor, his_mask: Tensor, packed: Encoder
         raise ValueError("batch must be positive")
     U = his_ids.shape[0]
     dev = news.device
-    icap = _interest_args(interest_cap, return_interest, score_type, news_cluster, cluster_cap, after)
     if out is not None and len(out) != (3 if return_interest else 2):
         raise ValueError("out must be (scores, ids), or (scores, ids, interests) with return_interest")
-    _no_cursor_under_caps(after, news_cluster, cluster_cap)
-    walk = _resume_args(resume, after, news_cluster is not None or cluster_cap is not None or icap > 0, U)
-    pri = _prior(news_bias, user_group, U, news.shape[0])
-    caps = _caps(news_cluster, cluster_cap, news.shape[0])
-    cur = _cursor(after, U)
-    _require_device(news, his_ids, his_mask, exclude_ids, eligible)
+    # (the exclusion matrix is put together before the options are checked: the request checks it too)
     excl = _exclusions(exclude_ids, exclude_history, his_ids, his_mask)
-    ok = None if eligible is None else _eligible_words(eligible, news.shape[0])   # packed once
-    sub = None if news_ids is None else _news_id_list(news_ids, news.shape[0])    # canonicalised once
+    # checked, packed and canonicalised once; sliced per batch
+    req = _request(U, news.shape[0], score_type=score_type, exclude_ids=excl, eligible=eligible, news_ids=news_ids,
+                   news_bias=news_bias, user_group=user_group, news_cluster=news_cluster, cluster_cap=cluster_cap,
+                   after=after, interest_cap=interest_cap, return_interest=return_interest, resume=resume)
+    _require_device(news, his_ids, his_mask)
     res = tuple(out) if out is not None else (torch.empty(U, topk, dtype=torch.float32, device=dev),
                                               torch.empty(U, topk, dtype=torch.int32, device=dev)) + \
         ((torch.empty(U, topk, dtype=torch.int32, device=dev),) if return_interest else ())
@@ -1233,11 +1243,7 @@ def rank_corpus(news: Tensor, his_ids: Tensor, his_mask: Tensor, packed: Encoder
         u1 = min(U, u0 + batch)
         mui, proj = encode_users(news, his_mask[u0:u1], packed, his_ids=his_ids[u0:u1],
                                  his_bias=None if his_bias is None else his_bias[u0:u1], with_proj=with_proj)
-        got = rank_topk(mui, proj, news, topk, score_type=score_type,
-                        exclude_ids=None if excl is None else excl[u0:u1], eligible=ok, news_ids=sub,
-                        news_bias=None if pri is None else pri.users(u0, u1), news_cluster=caps,
-                        after=None if cur is None else cur.users(u0, u1), interest_cap=interest_cap,
-                        return_interest=return_interest, resume=None if walk is None else walk.users(u0, u1))
-        for dst, src in zip(res, got):
+        _, _, mui, proj, tab = _rank_operands(mui, proj, news, score_type)
+        for dst, src in zip(res, _rank(mui, proj, tab, topk, req.users(u0, u1))):
             dst[u0:u1] = src
     return res

@@ -2012,6 +2012,46 @@ int rk_run(void* stream, int dtype, RkParams prm, void* workspace, size_t worksp
   return rk_dispatch(stream, dtype, prm, kRank);
 }
 
+// the fields every miner_rank_topk* entry point has; each entry sets what it adds by name. M = -1:
+// the whole table (a NULL id list)
+RkParams rk_params(int score_type, const void* user_mui, const void* user_proj, const void* news, int U, int N, int d, int K,
+                   int topk, float* top_scores, int32_t* top_ids) {
+  RkParams prm{};
+  prm.mui = user_mui; prm.proj = user_proj; prm.news = news; prm.top_s = top_scores; prm.top_i = top_ids;
+  prm.U = U; prm.N = N; prm.d = d; prm.K = K; prm.topk = topk; prm.score_type = score_type;
+  prm.M = -1;
+  return prm;
+}
+
+// every miner_score_pairs* entry point: the pairs are prm.ids [U][M], the scores go to prm.top_s and
+// the interests (NULL: not wanted) to prm.top_g
+int pair_run(void* stream, int dtype, RkParams prm) {
+  const int ck = rk_check_common(dtype, prm, false);
+  if (ck != MINER_OK) return ck;
+  if (prm.M < 0 || (prm.M > 0 && (!prm.ids || !prm.top_s))) return MINER_EINVAL;
+  if (!aligned4(prm.ids) || !aligned4(prm.top_s)) return MINER_EALIGN;
+  const int bk = bias_check(prm);
+  if (bk != MINER_OK) return bk;
+  // the interests: a score type that has a dominant interest, then the alignment
+  if (prm.top_g != nullptr && prm.score_type == MINER_SCORE_MEAN) return MINER_EINVAL;
+  if (!aligned4(prm.top_g)) return MINER_EALIGN;
+  if (prm.U == 0 || prm.M == 0) return MINER_OK;
+  return rk_dispatch(stream, dtype, prm, kPair);
+}
+
+// both miner_rank_count* entry points: the counts go to prm.top_i [U][T]
+int count_run(void* stream, int dtype, RkParams prm) {
+  const int ck = rk_check_common(dtype, prm, false);
+  if (ck != MINER_OK) return ck;
+  if (prm.T <= 0 || !prm.tgt_s || !prm.tgt_i || !prm.top_i) return MINER_EINVAL;
+  if (prm.T > kMaxT) return MINER_ESHAPE;
+  if (!aligned4(prm.tgt_s) || !aligned4(prm.tgt_i) || !aligned4(prm.ok) || !aligned4(prm.top_i)) return MINER_EALIGN;
+  const int bk = bias_check(prm);
+  if (bk != MINER_OK) return bk;
+  if (prm.U == 0) return MINER_OK;
+  return rk_dispatch(stream, dtype, prm, kCount);
+}
+
 // the checks the list-merge entry points start with, and their one launch
 int merge_check(const float* a_scores, const int32_t* a_ids, int ka, const float* b_scores, const int32_t* b_ids, int kb,
                 int U, int topk, const uint32_t* news_ok, int N, float* out_scores, int32_t* out_ids) {
@@ -2043,64 +2083,48 @@ extern "C" {
 
 int miner_score_pairs(void* stream, int dtype, int score_type, const void* user_mui, const void* user_proj,
                       const void* news, int U, int N, int d, int K, const int32_t* cand_ids, int C, float* scores) {
-  return miner_score_pairs_biased(stream, dtype, score_type, user_mui, user_proj, news, U, N, d, K, cand_ids, C, scores,
-                                  nullptr, 0, nullptr);
+  RkParams prm = rk_params(score_type, user_mui, user_proj, news, U, N, d, K, 0, scores, nullptr);
+  prm.ids = cand_ids; prm.M = C;
+  return pair_run(stream, dtype, prm);
 }
 
 int miner_score_pairs_biased(void* stream, int dtype, int score_type, const void* user_mui, const void* user_proj,
                              const void* news, int U, int N, int d, int K, const int32_t* cand_ids, int C, float* scores,
                              const float* news_bias, int G, const int32_t* user_group) {
-  return miner_score_pairs_interest(stream, dtype, score_type, user_mui, user_proj, news, U, N, d, K, cand_ids, C, scores,
-                                    news_bias, G, user_group, nullptr);
+  RkParams prm = rk_params(score_type, user_mui, user_proj, news, U, N, d, K, 0, scores, nullptr);
+  prm.ids = cand_ids; prm.M = C;
+  prm.bias = news_bias; prm.G = G; prm.grp = user_group;
+  return pair_run(stream, dtype, prm);
 }
 
 int miner_score_pairs_interest(void* stream, int dtype, int score_type, const void* user_mui, const void* user_proj,
                                const void* news, int U, int N, int d, int K, const int32_t* cand_ids, int C, float* scores,
                                const float* news_bias, int G, const int32_t* user_group, int32_t* interests) {
-  RkParams prm{};
-  prm.mui = user_mui; prm.proj = user_proj; prm.news = news; prm.top_s = scores;
-  prm.U = U; prm.N = N; prm.d = d; prm.K = K; prm.score_type = score_type;
+  RkParams prm = rk_params(score_type, user_mui, user_proj, news, U, N, d, K, 0, scores, nullptr);
   prm.ids = cand_ids; prm.M = C;
-  prm.bias = news_bias; prm.grp = user_group; prm.G = G;
+  prm.bias = news_bias; prm.G = G; prm.grp = user_group;
   prm.top_g = interests;
-  const int ck = rk_check_common(dtype, prm, false);
-  if (ck != MINER_OK) return ck;
-  if (C < 0 || (C > 0 && (!cand_ids || !scores))) return MINER_EINVAL;
-  if (!aligned4(cand_ids) || !aligned4(scores)) return MINER_EALIGN;
-  const int bk = bias_check(prm);
-  if (bk != MINER_OK) return bk;
-  // the interests: a score type that has a dominant interest, then the alignment
-  if (interests != nullptr && score_type == MINER_SCORE_MEAN) return MINER_EINVAL;
-  if (!aligned4(interests)) return MINER_EALIGN;
-  if (U == 0 || C == 0) return MINER_OK;
-  return rk_dispatch(stream, dtype, prm, kPair);
+  return pair_run(stream, dtype, prm);
 }
 
 int miner_rank_count(void* stream, int dtype, int score_type, const void* user_mui, const void* user_proj,
                      const void* news, int U, int N, int d, int K, const float* target_scores, const int32_t* target_ids,
                      int T, const uint32_t* news_ok, int32_t* counts) {
-  return miner_rank_count_biased(stream, dtype, score_type, user_mui, user_proj, news, U, N, d, K, target_scores, target_ids,
-                                 T, news_ok, counts, nullptr, 0, nullptr);
+  RkParams prm = rk_params(score_type, user_mui, user_proj, news, U, N, d, K, 0, nullptr, counts);
+  prm.M = 0;
+  prm.ok = news_ok; prm.tgt_s = target_scores; prm.tgt_i = target_ids; prm.T = T;
+  return count_run(stream, dtype, prm);
 }
 
 int miner_rank_count_biased(void* stream, int dtype, int score_type, const void* user_mui, const void* user_proj,
                             const void* news, int U, int N, int d, int K, const float* target_scores,
                             const int32_t* target_ids, int T, const uint32_t* news_ok, int32_t* counts,
                             const float* news_bias, int G, const int32_t* user_group) {
-  RkParams prm{};
-  prm.mui = user_mui; prm.proj = user_proj; prm.news = news; prm.top_i = counts;
-  prm.U = U; prm.N = N; prm.d = d; prm.K = K; prm.score_type = score_type;
+  RkParams prm = rk_params(score_type, user_mui, user_proj, news, U, N, d, K, 0, nullptr, counts);
+  prm.M = 0;
   prm.ok = news_ok; prm.tgt_s = target_scores; prm.tgt_i = target_ids; prm.T = T;
-  prm.bias = news_bias; prm.grp = user_group; prm.G = G;
-  const int ck = rk_check_common(dtype, prm, false);
-  if (ck != MINER_OK) return ck;
-  if (T <= 0 || !target_scores || !target_ids || !counts) return MINER_EINVAL;
-  if (T > kMaxT) return MINER_ESHAPE;
-  if (!aligned4(target_scores) || !aligned4(target_ids) || !aligned4(news_ok) || !aligned4(counts)) return MINER_EALIGN;
-  const int bk = bias_check(prm);
-  if (bk != MINER_OK) return bk;
-  if (U == 0) return MINER_OK;
-  return rk_dispatch(stream, dtype, prm, kCount);
+  prm.bias = news_bias; prm.G = G; prm.grp = user_group;
+  return count_run(stream, dtype, prm);
 }
 
 size_t miner_encoder_packed_bytes(int dtype, int d, int Dc, int K) {
@@ -2163,36 +2187,37 @@ int miner_rank_topk_split_recommended(int U) { return U > 0 && rk_split_wanted(U
 
 int miner_rank_topk(void* stream, int dtype, int score_type, const void* user_mui, const void* user_proj,
                     const void* news, int U, int N, int d, int K, int topk, float* top_scores, int32_t* top_ids) {
-  return miner_rank_topk_ws(stream, dtype, score_type, user_mui, user_proj, news, U, N, d, K, topk, top_scores, top_ids,
-                            nullptr, 0);
+  RkParams prm = rk_params(score_type, user_mui, user_proj, news, U, N, d, K, topk, top_scores, top_ids);
+  return rk_run(stream, dtype, prm, nullptr, 0);
 }
 
 int miner_rank_topk_ws(void* stream, int dtype, int score_type, const void* user_mui, const void* user_proj,
                        const void* news, int U, int N, int d, int K, int topk, float* top_scores, int32_t* top_ids,
                        void* workspace, size_t workspace_bytes) {
-  return miner_rank_topk_filtered(stream, dtype, score_type, user_mui, user_proj, news, U, N, d, K, topk, nullptr, 0,
-                                  nullptr, top_scores, top_ids, workspace, workspace_bytes);
+  RkParams prm = rk_params(score_type, user_mui, user_proj, news, U, N, d, K, topk, top_scores, top_ids);
+  return rk_run(stream, dtype, prm, workspace, workspace_bytes);
 }
 
 int miner_rank_topk_filtered(void* stream, int dtype, int score_type, const void* user_mui, const void* user_proj,
                              const void* news, int U, int N, int d, int K, int topk, const int32_t* exclude_ids, int E,
                              const uint32_t* news_ok, float* top_scores, int32_t* top_ids, void* workspace,
                              size_t workspace_bytes) {
-  return miner_rank_topk_after(stream, dtype, score_type, user_mui, user_proj, news, U, N, d, K, topk, exclude_ids, E, news_ok,
-                               nullptr, -1, top_scores, top_ids, workspace, workspace_bytes, nullptr, 0, nullptr, nullptr, 0,
-                               nullptr, nullptr);
+  RkParams prm = rk_params(score_type, user_mui, user_proj, news, U, N, d, K, topk, top_scores, top_ids);
+  prm.excl = exclude_ids; prm.E = E; prm.ok = news_ok;
+  return rk_run(stream, dtype, prm, workspace, workspace_bytes);
 }
 
 int miner_rank_topk_subset(void* stream, int dtype, int score_type, const void* user_mui, const void* user_proj,
                            const void* news, int U, int N, int d, int K, int topk, const int32_t* exclude_ids, int E,
                            const uint32_t* news_ok, const int32_t* news_ids, int M, float* top_scores, int32_t* top_ids,
                            void* workspace, size_t workspace_bytes) {
+  RkParams prm = rk_params(score_type, user_mui, user_proj, news, U, N, d, K, topk, top_scores, top_ids);
+  prm.excl = exclude_ids; prm.E = E; prm.ok = news_ok;
   // Here a NULL list with M < 0 is an error, for the wider entries it is the whole table: that pair
   // goes on with a list pointer that is never read, so that M < 0 answers at the list's check.
   static const int32_t no_list = 0;
-  return miner_rank_topk_after(stream, dtype, score_type, user_mui, user_proj, news, U, N, d, K, topk, exclude_ids, E, news_ok,
-                               news_ids == nullptr && M < 0 ? &no_list : news_ids, M, top_scores, top_ids, workspace,
-                               workspace_bytes, nullptr, 0, nullptr, nullptr, 0, nullptr, nullptr);
+  prm.ids = news_ids == nullptr && M < 0 ? &no_list : news_ids; prm.M = M;
+  return rk_run(stream, dtype, prm, workspace, workspace_bytes);
 }
 
 int miner_rank_topk_biased(void* stream, int dtype, int score_type, const void* user_mui, const void* user_proj,
@@ -2200,9 +2225,11 @@ int miner_rank_topk_biased(void* stream, int dtype, int score_type, const void* 
                            const uint32_t* news_ok, const int32_t* news_ids, int M, float* top_scores, int32_t* top_ids,
                            void* workspace, size_t workspace_bytes, const float* news_bias, int G,
                            const int32_t* user_group) {
-  return miner_rank_topk_after(stream, dtype, score_type, user_mui, user_proj, news, U, N, d, K, topk, exclude_ids, E, news_ok,
-                               news_ids, M, top_scores, top_ids, workspace, workspace_bytes, news_bias, G, user_group, nullptr,
-                               0, nullptr, nullptr);
+  RkParams prm = rk_params(score_type, user_mui, user_proj, news, U, N, d, K, topk, top_scores, top_ids);
+  prm.excl = exclude_ids; prm.E = E; prm.ok = news_ok;
+  prm.ids = news_ids; prm.M = M;
+  prm.bias = news_bias; prm.G = G; prm.grp = user_group;
+  return rk_run(stream, dtype, prm, workspace, workspace_bytes);
 }
 
 int miner_rank_topk_capped(void* stream, int dtype, int score_type, const void* user_mui, const void* user_proj,
@@ -2210,9 +2237,12 @@ int miner_rank_topk_capped(void* stream, int dtype, int score_type, const void* 
                            const uint32_t* news_ok, const int32_t* news_ids, int M, float* top_scores, int32_t* top_ids,
                            void* workspace, size_t workspace_bytes, const float* news_bias, int G,
                            const int32_t* user_group, const int32_t* news_cluster, int cap) {
-  return miner_rank_topk_after(stream, dtype, score_type, user_mui, user_proj, news, U, N, d, K, topk, exclude_ids, E, news_ok,
-                               news_ids, M, top_scores, top_ids, workspace, workspace_bytes, news_bias, G, user_group,
-                               news_cluster, cap, nullptr, nullptr);
+  RkParams prm = rk_params(score_type, user_mui, user_proj, news, U, N, d, K, topk, top_scores, top_ids);
+  prm.excl = exclude_ids; prm.E = E; prm.ok = news_ok;
+  prm.ids = news_ids; prm.M = M;
+  prm.bias = news_bias; prm.G = G; prm.grp = user_group;
+  prm.clus = news_cluster; prm.cap = cap;
+  return rk_run(stream, dtype, prm, workspace, workspace_bytes);
 }
 
 int miner_rank_topk_after(void* stream, int dtype, int score_type, const void* user_mui, const void* user_proj,
@@ -2221,9 +2251,13 @@ int miner_rank_topk_after(void* stream, int dtype, int score_type, const void* u
                           void* workspace, size_t workspace_bytes, const float* news_bias, int G,
                           const int32_t* user_group, const int32_t* news_cluster, int cap, const float* after_scores,
                           const int32_t* after_ids) {
-  return miner_rank_topk_interest(stream, dtype, score_type, user_mui, user_proj, news, U, N, d, K, topk, exclude_ids, E,
-                                  news_ok, news_ids, M, top_scores, top_ids, workspace, workspace_bytes, news_bias, G,
-                                  user_group, news_cluster, cap, after_scores, after_ids, 0, nullptr);
+  RkParams prm = rk_params(score_type, user_mui, user_proj, news, U, N, d, K, topk, top_scores, top_ids);
+  prm.excl = exclude_ids; prm.E = E; prm.ok = news_ok;
+  prm.ids = news_ids; prm.M = M;
+  prm.bias = news_bias; prm.G = G; prm.grp = user_group;
+  prm.clus = news_cluster; prm.cap = cap;
+  prm.aft_s = after_scores; prm.aft_i = after_ids;
+  return rk_run(stream, dtype, prm, workspace, workspace_bytes);
 }
 
 int miner_rank_topk_interest(void* stream, int dtype, int score_type, const void* user_mui, const void* user_proj,
@@ -2232,18 +2266,14 @@ int miner_rank_topk_interest(void* stream, int dtype, int score_type, const void
                              void* workspace, size_t workspace_bytes, const float* news_bias, int G,
                              const int32_t* user_group, const int32_t* news_cluster, int cap, const float* after_scores,
                              const int32_t* after_ids, int interest_cap, int32_t* top_interest) {
-  RkParams prm{};
-  prm.mui = user_mui; prm.proj = user_proj; prm.news = news; prm.top_s = top_scores; prm.top_i = top_ids;
-  prm.U = U; prm.N = N; prm.d = d; prm.K = K; prm.topk = topk; prm.score_type = score_type;
+  RkParams prm = rk_params(score_type, user_mui, user_proj, news, U, N, d, K, topk, top_scores, top_ids);
   prm.excl = exclude_ids; prm.E = E; prm.ok = news_ok;
-  prm.ids = news_ids; prm.M = M;           // the whole table: a NULL list with M < 0
-  prm.bias = news_bias; prm.grp = user_group; prm.G = G;
+  prm.ids = news_ids; prm.M = M;
+  prm.bias = news_bias; prm.G = G; prm.grp = user_group;
   prm.clus = news_cluster; prm.cap = cap;
   prm.aft_s = after_scores; prm.aft_i = after_ids;
-  return miner_rank_topk_resume(stream, dtype, score_type, user_mui, user_proj, news, U, N, d, K, topk, exclude_ids, E,
-                                news_ok, news_ids, M, top_scores, top_ids, workspace, workspace_bytes, news_bias, G,
-                                user_group, news_cluster, cap, after_scores, after_ids, interest_cap, top_interest, nullptr,
-                                nullptr, nullptr, 0);
+  prm.icap = interest_cap; prm.top_g = top_interest;
+  return rk_run(stream, dtype, prm, workspace, workspace_bytes);
 }
 
 int miner_rank_topk_resume(void* stream, int dtype, int score_type, const void* user_mui, const void* user_proj,
@@ -2253,12 +2283,10 @@ int miner_rank_topk_resume(void* stream, int dtype, int score_type, const void* 
                            const int32_t* user_group, const int32_t* news_cluster, int cap, const float* after_scores,
                            const int32_t* after_ids, int interest_cap, int32_t* top_interest, const int32_t* used_groups,
                            const int32_t* used_counts, const int32_t* n_used, int Q) {
-  RkParams prm{};
-  prm.mui = user_mui; prm.proj = user_proj; prm.news = news; prm.top_s = top_scores; prm.top_i = top_ids;
-  prm.U = U; prm.N = N; prm.d = d; prm.K = K; prm.topk = topk; prm.score_type = score_type;
+  RkParams prm = rk_params(score_type, user_mui, user_proj, news, U, N, d, K, topk, top_scores, top_ids);
   prm.excl = exclude_ids; prm.E = E; prm.ok = news_ok;
-  prm.ids = news_ids; prm.M = M;           // the whole table: a NULL list with M < 0
-  prm.bias = news_bias; prm.grp = user_group; prm.G = G;
+  prm.ids = news_ids; prm.M = M;
+  prm.bias = news_bias; prm.G = G; prm.grp = user_group;
   prm.clus = news_cluster; prm.cap = cap;
   prm.aft_s = after_scores; prm.aft_i = after_ids;
   prm.icap = interest_cap; prm.top_g = top_interest;

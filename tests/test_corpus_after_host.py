@@ -190,7 +190,7 @@ def test_start_and_page_cursor_on_cpu_tensors():
 @pytest.fixture(scope="module")
 def driver():
     try:
-        return build.build_asan_driver_after()
+        return build.build_asan_driver(driver="after")
     except RuntimeError as e:                       # no ROCm toolchain in this environment
         pytest.skip(f"asan build unavailable: {e}")
 

@@ -186,7 +186,7 @@ def test_python_argument_errors():
 @pytest.fixture(scope="module")
 def driver():
     try:
-        return build.build_asan_driver_bias()
+        return build.build_asan_driver(driver="bias")
     except RuntimeError as e:                       # no ROCm toolchain in this environment
         pytest.skip(f"asan build unavailable: {e}")
 

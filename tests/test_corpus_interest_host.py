@@ -246,7 +246,7 @@ def test_python_argument_errors():
 @pytest.fixture(scope="module")
 def driver():
     try:
-        return build.build_asan_driver_interest()
+        return build.build_asan_driver(driver="interest")
     except RuntimeError as e:                       # no ROCm toolchain in this environment
         pytest.skip(f"asan build unavailable: {e}")
 

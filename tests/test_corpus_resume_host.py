@@ -300,7 +300,7 @@ def test_advance_walk_argument_errors():
 @pytest.fixture(scope="module")
 def driver():
     try:
-        return build.build_asan_driver_resume()
+        return build.build_asan_driver(driver="resume")
     except RuntimeError as e:                       # no ROCm toolchain in this environment
         pytest.skip(f"asan build unavailable: {e}")
 

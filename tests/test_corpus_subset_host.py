@@ -105,7 +105,7 @@ def test_merge_argument_errors_before_any_launch(lib):
 @pytest.fixture(scope="module")
 def driver():
     try:
-        return build.build_asan_driver_subset()
+        return build.build_asan_driver(driver="subset")
     except RuntimeError as e:                       # no ROCm toolchain in this environment
         pytest.skip(f"asan build unavailable: {e}")
 
