@@ -70,6 +70,8 @@ SIGNATURES = {
     "miner_rank_topk_resume": (_I, [_P, _I, _I, _P, _P, _P, _I, _I, _I, _I, _I, _P, _I, _P, _P, _I, _P, _P, _P,
                                     ctypes.c_size_t, _P, _I, _P, _P, _I, _P, _P, _I, _P, _P, _P, _P, _I]),
     "miner_walk_advance": (_I, [_P, _P, _P, _P, _P, _I, _P, _P, _P, _I, _P, _P, _P, _P, _P, _P, _I, _I, _I]),
+    # include/miner_diversify.h
+    "miner_topk_diversify": (_I, [_P, _I, _P, _I, _I, _P, _P, _I, _I, _I, ctypes.c_float, _I, _P, _P, _P, _P]),
     # include/miner_news.h
     "miner_news_precompute": (_I, [_P, _I, _P, _I, _P, _I, _I, _I, _P, _P]),
     "miner_score_news": (_I, [_P, _I, _I, _P, _P, _P, _I, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P]),

@@ -18,8 +18,8 @@ SRC = os.path.join(HERE, "csrc", "miner_score.hip")      # the fused scoring ker
 SOURCES = [SRC, os.path.join(HERE, "csrc", "miner_metrics.hip"), os.path.join(HERE, "csrc", "fastformer.hip"),
            os.path.join(HERE, "csrc", "corpus.hip"), os.path.join(HERE, "csrc", "news.hip"),
            os.path.join(HERE, "csrc", "miner_auc.hip"), os.path.join(HERE, "csrc", "wide.hip"),
-           os.path.join(HERE, "csrc", "news_x2.hip")]
-HEADERS = [os.path.join(ROOT, "include", h) for h in ("miner_score.h", "miner_metrics.h", "miner_fastformer.h", "miner_corpus.h", "miner_news.h", "miner_wide.h")] + [os.path.join(HERE, "csrc", "cdna4_common.h")]
+           os.path.join(HERE, "csrc", "news_x2.hip"), os.path.join(HERE, "csrc", "diversify.hip")]
+HEADERS = [os.path.join(ROOT, "include", h) for h in ("miner_score.h", "miner_metrics.h", "miner_fastformer.h", "miner_corpus.h", "miner_news.h", "miner_wide.h", "miner_diversify.h")] + [os.path.join(HERE, "csrc", "cdna4_common.h")]
 LIB = os.path.join(HERE, "libminer_hip.so")
 ARCH = os.environ.get("MINER_OFFLOAD_ARCH", "gfx950")
 
@@ -122,7 +122,8 @@ ASAN_DRIVER_DIR = os.path.join(ROOT, "tests", "native")
 
 def asan_drivers() -> dict:
     """The stand-alone drivers under tests/native/ by short name: "" is abi_errors.cpp (every entry
-    point), "resume" abi_errors_resume.cpp (one feature's entries; run by tests/test_corpus_resume_host.py)."""
+    point), "resume" abi_errors_resume.cpp (one feature's entries; run by tests/test_corpus_resume_host.py),
+    "diversify" abi_errors_diversify.cpp (tests/test_corpus_diversify_host.py)."""
     import glob
     return {os.path.basename(p)[len("abi_errors"):-len(".cpp")].lstrip("_"): p
             for p in sorted(glob.glob(os.path.join(ASAN_DRIVER_DIR, "abi_errors*.cpp")))}

@@ -33,6 +33,8 @@ d=768, fp16), backed by libminer_hip.so (include/miner_corpus.h).
     page = rank_topk(..., cluster_cap=1, resume=state)     # the per-group counts of the pages served so far;
     state = advance_walk(state, page, news_cluster=story)  # advanced on the device; also rank_corpus(resume=) and
     deep = rank_topk_deep_capped(..., 1000, cluster_cap=1) # capped lists of any depth (not merge_topk / update_topk / cap_topk)
+    page = diversify_topk(pool, news_table, 50, lam=0.7)   # diversity re-ranking (MMR) of a ranked pool of <= 256 entries
+    page = rank_topk_diverse(mui, proj, news_table, 50)    # by the table's own cosine similarity; rank_topk + diversify_topk
 
 The click score of (user, news) is the reference's (src/model/model.py:127-134, 213-214) with the
 impression's candidate set replaced by the whole news table; ties rank the lower news id first.
@@ -930,6 +932,109 @@ def cap_topk(lists, news_cluster, cluster_cap: int, topk: Optional[int] = None):
         raise ValueError("lists must hold at least one entry per user")
     return merge_topk((s[:, :0], i[:, :0]), (s, i), s.shape[1] if topk is None else topk, news_cluster=caps.cluster,
                       cluster_cap=caps.cap)
+
+
+MAX_POOL = 256
+_RELEVANCE = {"score": 0, "minmax": 1}          # MINER_DIVERSIFY_REL_* of include/miner_diversify.h
+
+
+def _mmr_args(lam, relevance) -> tuple:
+    """The checked (lambda, relevance code) of the diversity re-ranking."""
+    if isinstance(lam, bool) or not isinstance(lam, (int, float)) or not 0.0 <= lam <= 1.0:    # (NaN fails both)
+        raise ValueError("lam must be a number in [0, 1]")
+    if not isinstance(relevance, str) or relevance not in _RELEVANCE:
+        raise ValueError(f"relevance must be one of {sorted(_RELEVANCE)}")
+    return float(lam), _RELEVANCE[relevance]
+
+
+def diversify_topk(lists, news: Tensor, topk: Optional[int] = None, *, lam: float = 0.7, relevance: str = "minmax",
+                   return_positions: bool = False, return_objective: bool = False):
+    """Diversity re-ranking (maximal marginal relevance) of per-user pools on the device: ``lists`` =
+    (scores [U,P] fp32, ids [U,P] integer), P <= 256 — a list of rank_topk / merge_topk /
+    rank_topk_deep[:, :256], or any rows of pairs, in the order given — re-ordered by a greedy walk
+    that trades an entry's relevance against its cosine similarity, in the space of the table
+    ``news`` [N, d] (fp16, bf16 or fp32; d as the ranker takes it), to what the walk already listed:
+
+        pick the unlisted candidate p that maximises  lam · rel_p − (1 − lam) · max_{q listed} sim_pq
+
+    ``topk`` times (default P), ties to the lower position. An entry is a candidate iff its id is in
+    [0, N) and its score finite: the (-inf, -1) tail of a short list, ids outside the table and NaN /
+    infinite scores are never listed and no row is read for them; a repeated id is a candidate at
+    each position. ``relevance`` 'minmax' (default) scales the user's candidate scores to [0, 1]
+    (rel = 0 when they are all equal) so that ``lam`` means the same for every user, 'score' takes
+    them as they are. sim is the cosine of the table rows, the products accumulated in fp32 on the
+    matrix cores, 0 for an all-zero row or a row that holds an inf / NaN. All arithmetic of the
+    objective is fp32 (include/miner_diversify.h is the contract; tests/diversify_ref.py restates it).
+
+    Returns (scores [U,topk] fp32, ids [U,topk] int32): the listed entries with their input scores
+    bit for bit, then (-inf, -1) once the candidates ran out. A (scores, ids, interests) triple comes
+    back as a triple, each entry with its interest (-1 in the tail). ``return_positions`` appends
+    positions int32 [U,topk], where in the pool each entry stood (-1 in the tail);
+    ``return_objective`` appends the fp32 objective each entry had when it was picked (-inf in the
+    tail). lam = 1 lists the candidates by relevance, ties by position: a ranked list's own prefix.
+    The result is a subset of the pool, so a pool ranked under caps (news_cluster / cluster_cap,
+    interest_cap) keeps them; it is NOT in score order: not an input for merge_topk / update_topk /
+    page_cursor. Users are independent: a batch gives what its users give alone, bit for bit. One
+    launch, one workgroup per user; the price against the rank step: profiles/rk_diversify_ab.txt."""
+    lam, rel = _mmr_args(lam, relevance)
+    triple = _is_triple(lists)
+    s, i, *g = _list_triple(lists, "lists") if triple else _list_pair(lists, "lists")
+    U, P = s.shape
+    if P < 1:
+        raise ValueError("lists must hold at least one entry per user")
+    topk = P if topk is None else topk
+    if isinstance(topk, bool) or not isinstance(topk, int) or not 1 <= topk <= P:
+        raise ValueError(f"topk must be an int in [1, {P}], the pool's width")
+    if not isinstance(news, Tensor) or news.dim() != 2 or news.shape[0] < 1:
+        raise ValueError("news must be a table [N, d] with N >= 1")
+    dt = _code(news.dtype)
+    N, d = news.shape
+    if d < 1 or d > 1024 or d % (32 if dt == _lib.DTYPE_F32 else 64):
+        raise ValueError(f"d = {d}: the table's width must be a multiple of 64 (float32: of 32), at most 1024")
+    _require_device(s, i, *g, news)
+    tab = news.contiguous()
+    dev = tab.device
+    if s.device != dev or i.device != dev or any(x.device != dev for x in g):
+        raise ValueError("lists and news must be on one device")
+    out_s = torch.empty(U, topk, dtype=torch.float32, device=dev)
+    out_i = torch.empty(U, topk, dtype=torch.int32, device=dev)
+    out_p = torch.empty(U, topk, dtype=torch.int32, device=dev)
+    out_o = torch.empty(U, topk, dtype=torch.float32, device=dev) if return_objective else None
+    with torch.cuda.device(dev):
+        rc = _lib.lib().miner_topk_diversify(_stream(dev), dt, _ptr(tab), N, d, _ptr(s), _ptr(i), U, P, topk, lam, rel,
+                                             _ptr(out_s), _ptr(out_i), _ptr(out_p), _ptr(out_o))
+    _lib.check(rc, "miner_topk_diversify")
+    out = (out_s, out_i)
+    if triple:
+        listed = out_p >= 0
+        out += (torch.where(listed, g[0].gather(1, out_p.clamp(min=0).to(torch.int64)), -1).to(torch.int32),)
+    if return_positions:
+        out += (out_p,)
+    if return_objective:
+        out += (out_o,)
+    return out
+
+
+def rank_topk_diverse(user_mui: Tensor, user_proj: Optional[Tensor], news: Tensor, topk: int, *,
+                      pool: Optional[int] = None, lam: float = 0.7, relevance: str = "minmax", **rank_kwargs):
+    """rank_topk, then diversify_topk: the ``pool`` best news per user (default min(256, 4 · topk);
+    topk <= pool <= 256) ranked with rank_topk(..., topk=pool, **rank_kwargs), re-ranked to ``topk`` by
+    diversify_topk(..., lam=, relevance=) against the same table — bit for bit those two calls.
+    Everything else is rank_topk's and passes through unchanged: score_type, exclude_ids, eligible,
+    news_ids, news_bias / user_group, news_cluster / cluster_cap, interest_cap, after,
+    return_interest (the result is then a triple). The page is a subset of the pool, so a pool ranked
+    under caps keeps its caps. ``resume=`` is refused: a diversified page is not a page of a walk (it
+    is not in score order and does not end where the next page would begin)."""
+    if rank_kwargs.get("resume") is not None:
+        raise ValueError("rank_topk_diverse: a diversified page is not a walk page, there is no resume=")
+    lam, _ = _mmr_args(lam, relevance)
+    if isinstance(topk, bool) or not isinstance(topk, int) or not 1 <= topk <= MAX_POOL:
+        raise ValueError(f"topk must be an int in [1, {MAX_POOL}]")
+    pool = min(MAX_POOL, 4 * topk) if pool is None else pool
+    if isinstance(pool, bool) or not isinstance(pool, int) or not topk <= pool <= MAX_POOL:
+        raise ValueError(f"pool must be an int in [topk, {MAX_POOL}]: the re-ranking chooses topk = {topk} of the pool")
+    return diversify_topk(rank_topk(user_mui, user_proj, news, pool, **rank_kwargs), news, topk, lam=lam,
+                          relevance=relevance)
 
 
 MAX_TARGETS = 64
